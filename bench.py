@@ -3,6 +3,7 @@
 matrix on the host) on N x MI355X.
 
     python bench.py --gpus 1 --steps 5 --warmup 2
+    python bench.py --gpus 1 --steps 5 --warmup 2 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -12,6 +13,11 @@ GPU-share drawn from the 10x 737K whitelist, 16 bp CB + 10 bp UMI, 30 000 genes,
 cell ids, UMI de-duplication (radix sort + segmented reduces), per-cell sizes, real/filtered cells, and
 both count matrices copied to the host.  Inputs are resident in HBM before the timed region.
 Prints ONE JSON line (rank 0).
+
+A plain run sets up, warms up, times the steps (`value`, `ms_per_step`, and `roofline` of the dominant kernel from the events
+inside the timed region) and writes the last step's outputs when --dump-outputs is given.  --full adds everything that takes
+runs of its own: the kernel-table pass and the whole-pipeline roofline, the other matrix forms, the CPU oracle baseline, the
+PCIe-inclusive ingest rates and, on the default C2 run, secondary.c3_1e9, secondary.c2_sharded_runner and secondary.bam_ingest.
 """
 import argparse
 import json
@@ -60,12 +66,20 @@ def parse():
                          "first-contact check of the multi-GPU command on a one-GPU box, not a measurement")
     ap.add_argument("--one-device", action="store_true", help="every rank uses GPU 0 (with --backend gloo and DROPEST_SHARD_DATAPLANE=shm)")
     ap.add_argument("--dump-matrices", default="", help="rank 0: write cm / cm_raw of the last timed step (colptr, rows, values, column barcodes) to this .npz")
-    ap.add_argument("--no-secondary", action="store_true", help="default run only: skip the C3 line at 1e9 reads (secondary.c3_1e9)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0: write what the last timed step returned as DIR/<name>.npy in float64 (a seeded sample of the matrices' entries)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: kernel table, pipeline roofline, matrix forms, CPU baseline, ingest rates, "
+                         "and on the default C2 run the secondary lines")
+    ap.add_argument("--no-secondary", action="store_true", help="--full default run only: skip the secondary lines (C3 at 1e9 reads, sharded runner, BAM ingest)")
     ap.add_argument("--push-sample", type=float, default=float(os.environ.get("DROPEST_BENCH_PUSH_SAMPLE", 5e7)),
                     help="reads pushed from pinned host memory for the PCIe-inclusive rates (c2, N=1; 0 disables)")
     ap.add_argument("--cpu-sample", type=float, default=float(os.environ.get("DROPEST_BENCH_CPU_SAMPLE", 6e6)),
                     help="reads of the same stream timed on the CPU oracle (rank 0, N=1 only; 0 disables)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def matrix_form():
@@ -118,6 +132,64 @@ def dump_matrices(path, out, sharded):
             colptr, rows, vals = m[0], m[1], m[2]
             arrays.update({name + "_colptr": np.asarray(colptr, np.uint64), name + "_rows": np.array(rows, np.uint32), name + "_vals": np.array(vals, np.uint32)})
     np.savez(path, **arrays)
+
+
+DUMP_SAMPLE = 1 << 18          # matrix entries / cells written per array (all of them when there are fewer)
+DUMP_SEED = 20261016
+DUMP_LIMIT = 64 << 20          # bytes of .npy data at most
+
+
+def _dump_sample(n):
+    """The positions written of an output of n items: all of them, or a seeded sample of DUMP_SAMPLE in order."""
+    if n <= DUMP_SAMPLE:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE, replace=False))
+
+
+def dump_outputs(path, out, sharded, ctx):
+    """What the last timed step handed to its caller, as float64 arrays (every value is an integer below 2**53, so exact): per count
+    matrix the whole colptr, the sum of every column's values, and a seeded sample of its entries (position, column, row, value);
+    then the filtered cells and a seeded sample of merge_targets() (cell id, its target: itself where the CB merge folded nothing)
+    -- or, from the sharded runner, the matrix's column barcodes.  An array that comes out empty is not written."""
+    from dropest_amd.capi import Context
+    from dropest_amd.multi import widen_shard_matrix
+    arrays = {}
+    for name, m in (("cm", out[0]), ("cm_raw", out[1])):
+        if sharded:
+            colptr, rows, vals = widen_shard_matrix(m)[:3]
+        elif hasattr(m, "nnz"):
+            colptr, rows, vals = ctx.widen_bytes(m)
+        elif len(m) == 5:
+            colptr, rows, vals = Context.widen(m)
+        else:
+            colptr, rows, vals = m[0], m[1], m[2]
+        colptr = np.asarray(colptr, np.int64)
+        at = _dump_sample(len(rows))
+        csum = np.concatenate([[0], np.cumsum(vals, dtype=np.uint64)])
+        arrays.update({name + "_colptr": colptr, name + "_col_sum": csum[colptr[1:]] - csum[colptr[:-1]], name + "_sample_index": at,
+                       name + "_sample_col": np.searchsorted(colptr, at, side="right") - 1, name + "_sample_row": np.asarray(rows)[at],
+                       name + "_sample_value": np.asarray(vals)[at]})
+    if sharded:
+        arrays["cm_col_barcodes"] = out[2]
+    else:
+        arrays["filtered_cells"] = out[2]
+        src, tgt = out[3]                   # (the pairs the step fetched; Context.merge_targets() builds the same vector)
+        targets = np.arange(ctx.total_cells_number(), dtype=np.uint64)
+        targets[np.asarray(src, np.int64)] = tgt
+        at = _dump_sample(len(targets))
+        arrays["merge_targets_sample_index"], arrays["merge_targets_sample_value"] = at, targets[at]
+    arrays = {name: np.asarray(a) for name, a in arrays.items() if np.asarray(a).size}
+    total = 0
+    for name, a in arrays.items():
+        if int(a.max()) >= 1 << 53:
+            raise ValueError("--dump-outputs: %s holds values that float64 does not keep exactly" % name)
+        arrays[name] = a.astype(np.float64)
+        total += arrays[name].nbytes
+    if total > DUMP_LIMIT:
+        raise ValueError("--dump-outputs: %d bytes, more than the %d allowed" % (total, DUMP_LIMIT))
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def nnz_of(m):
@@ -268,8 +340,9 @@ def facade_add_record_rate(n=4_000_000):
         return {}
 
 
-def measure(args, config, reads_per_gpu, cells, steps, warmup, world, rank, local_rank, dist, force_sharded, with_ingest):
-    """Times `steps` passes of one workload; returns the bench line (rank 0) or None."""
+def measure(args, config, reads_per_gpu, cells, steps, warmup, world, rank, local_rank, dist, force_sharded, with_ingest, full, dump=False):
+    """Times `steps` passes of one workload; returns the bench line (rank 0) or None.  full: also the kernel-table pass, the other
+    matrix forms, the CPU baseline and the ingest rates, after the timed region.  dump: --dump-outputs applies to this workload."""
     import torch
     from dropest_amd import capi
     from dropest_amd.synth import SynthStream
@@ -346,14 +419,18 @@ def measure(args, config, reads_per_gpu, cells, steps, warmup, world, rank, loca
     fence()
     elapsed = time.perf_counter() - t0
     stats = get_stats()
+    if dump and rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, world > 1 or force_sharded, ctx)
     table_steps = max(1, min(3, steps))
-    set_prof(True)
-    for _ in range(table_steps):
-        step()
-    fence()
-    table = get_stats()
-    shard_phases = run.shard.phase_stats() if (world > 1 or force_sharded) else {}
-    sizes = ctx.table_sizes()
+    table, shard_phases, sizes = {}, {}, None
+    if full:
+        set_prof(True)
+        for _ in range(table_steps):
+            step()
+        fence()
+        table = get_stats()
+        shard_phases = run.shard.phase_stats() if (world > 1 or force_sharded) else {}
+        sizes = ctx.table_sizes()
     set_prof(False)
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if dist.get_backend() == "gloo" else "cuda")
@@ -397,12 +474,13 @@ def measure(args, config, reads_per_gpu, cells, steps, warmup, world, rank, loca
                                   for k, v in sorted(cands.items(), key=lambda kv: -kv[1]["ms"])[:6] if v["ms"] > 0}
         # whole-pipeline roofline: compulsory traffic = every packed record read once, every output item
         # written once: 24 B/read + 24 B/molecule + 12 B/matrix entry + 40 B/cell, over the sum of the kernel times
+        # (--full only: the table pass is what times every kernel)
         cm_nnz, raw_nnz = nnz_of(out[0]), nnz_of(out[1])
-        compulsory = 24.0 * sizes["reads"] + 24.0 * sizes["molecules"] + 12.0 * (cm_nnz + raw_nnz) / max(1, world) + 40.0 * sizes["cells"]
         t_kernels_ms = sum(v["ms"] for k, v in table.items() if not k.startswith("host:")) / table_steps
-        rec = pmc_record(config, reads_per_gpu, get_layout()["sort"])
-        measured = rec["hbm_bytes_per_step"] if rec else None
         if roof is not None and t_kernels_ms > 0:
+            compulsory = 24.0 * sizes["reads"] + 24.0 * sizes["molecules"] + 12.0 * (cm_nnz + raw_nnz) / max(1, world) + 40.0 * sizes["cells"]
+            rec = pmc_record(config, reads_per_gpu, get_layout()["sort"])
+            measured = rec["hbm_bytes_per_step"] if rec else None
             # every kernel of the pass weighted by its time: sum of the algorithmic bytes DESIGN.md section 2 states per kernel over the sum of
             # the kernel times of the table pass (events on every launch), against the peak
             alg_all = sum(v["bytes"] for k, v in table.items() if not k.startswith("host:")) / table_steps
@@ -433,15 +511,15 @@ def measure(args, config, reads_per_gpu, cells, steps, warmup, world, rank, loca
                             "GB_per_s_per_gpu": round(a2a["bytes"] / a2a["ms"] / 1e6, 1), "GB_per_s_per_link": round(a2a["bytes"] / a2a["ms"] / 1e6 / links, 1),
                             "links": links, "transport": "RCCL grouped ncclSend/ncclRecv over xGMI" if world > 1 else "one GPU: no peer -- the block a shard keeps is unpacked where the partition left it (no copy), so nothing moves here; the links' share is the table above"}
         cpu = None
-        if world == 1 and args.cpu_sample > 0:
+        if full and world == 1 and args.cpu_sample > 0:
             cpu = cpu_baseline(stream, int(min(args.cpu_sample, total_reads)), cfg, config.upper())
         ingest = None
-        if with_ingest and world == 1 and not force_sharded and args.push_sample > 0 and not merge:
+        if full and with_ingest and world == 1 and not force_sharded and args.push_sample > 0 and not merge:
             ingest = push_rates(stream, local_rank, int(min(args.push_sample, total_reads)),
                                 dict(merge_kind=capi.MERGE_NONE, min_genes_before_merge=cfg["min_before"], min_genes_after_merge=cfg["min_after"]))
         cm = out[0]
         forms = None
-        if world == 1 and not force_sharded and matrix_form() == "u32" and not os.environ.get("DROPEST_BENCH_NO_FORMS"):
+        if full and world == 1 and not force_sharded and matrix_form() == "u32" and not os.environ.get("DROPEST_BENCH_NO_FORMS"):
             # the same step with the matrices leaving in the other forms (3 steps each, after the timed region): the wire forms alone (their
             # consumer still has to decode them) and the 32-bit arrays copied over PCIe as they are
             forms = {}
@@ -472,7 +550,7 @@ def measure(args, config, reads_per_gpu, cells, steps, warmup, world, rank, loca
                        "merge_targets_fetched_per_step": int(len(out[3][0])) if len(out) > 3 and out[3] is not None else None, "sort_layout": get_layout(),
                        "matrix_form": form_text(cm, out[1]), "matrix_forms": forms},
             "roofline": roof, "cpu_baseline": cpu, "exchange": exchange, "host_ingest": ingest, "step_ms": step_ms, "kernels_ms_per_step": kernels,
-            "kernel_table": "separate pass of %d steps after the timed region, events on every launch" % table_steps,
+            "kernel_table": "separate pass of %d steps after the timed region, events on every launch" % table_steps if full else None,
             "host_stage_wall_ms_per_step": host_stages,
         }
     # give the device memory back before another workload is measured
@@ -672,15 +750,15 @@ def main():
             dist.init_process_group("nccl", device_id=torch.device("cuda", local_rank))
 
     rccl_came_up = False
-    line = measure(args, args.config, int(args.reads), args.cells, args.steps, args.warmup, world, rank, local_rank, dist, force_sharded, True)
+    line = measure(args, args.config, int(args.reads), args.cells, args.steps, args.warmup, world, rank, local_rank, dist, force_sharded, True, args.full, dump=True)
     # The largest single-GPU configuration of BASELINE.json (configs[2], "C3": 1e9 reads, 50 000 cells, whitelist CB merge) rides
-    # along with the default run as `secondary.c3_1e9` -- same clock, same fences, 5 timed steps after 1 warm-up (24 GB of reads).
-    if (line is not None and world == 1 and not force_sharded and args.config == "c2" and int(args.reads) == 100_000_000 and not args.no_secondary
+    # along with the default run under --full as `secondary.c3_1e9` -- same clock, same fences, 5 timed steps after 1 warm-up (24 GB of reads).
+    if (args.full and line is not None and world == 1 and not force_sharded and args.config == "c2" and int(args.reads) == 100_000_000 and not args.no_secondary
             and not args.merge_umi):
         try:
             full_sample, args.cpu_sample = args.cpu_sample, min(args.cpu_sample, 1.5e6)   # (the oracle with the whitelist merge runs at ~0.12 Mreads/s: 12 s for 1.5e6 reads)
             try:
-                sec = measure(args, "c3", 1_000_000_000, 50000, 5, 1, world, rank, local_rank, dist, False, False)
+                sec = measure(args, "c3", 1_000_000_000, 50000, 5, 1, world, rank, local_rank, dist, False, False, True)
             finally:
                 args.cpu_sample = full_sample
             line["secondary"] = {"c3_1e9": {k: sec[k] for k in ("value", "unit", "ms_per_step", "steps", "warmup", "step_ms", "config", "roofline", "cpu_baseline",
@@ -696,7 +774,7 @@ def main():
             os.dup2(2, 1)          # (RCCL's banner)
             cpu_sample, args.cpu_sample = args.cpu_sample, 0
             try:
-                sh = measure(args, "c2", 100_000_000, args.cells, args.steps, args.warmup, world, rank, local_rank, dist, True, False)
+                sh = measure(args, "c2", 100_000_000, args.cells, args.steps, args.warmup, world, rank, local_rank, dist, True, False, True)
             finally:
                 args.cpu_sample = cpu_sample
                 sys.stdout.flush()
@@ -723,7 +801,7 @@ def main():
             line["secondary"]["c2_sharded_runner"] = {"error": "%s: %s" % (type(e).__name__, e)}
     # What feeds the pass from a file: a synthetic 10x BAM through BamController into the container, by the host reader and by
     # the device path (BGZF inflate + record walk + tag parse on the GPU, include/dropest_bgzf.h), and the inflate kernel alone.
-    if (line is not None and world == 1 and not force_sharded and args.config == "c2" and int(args.reads) == 100_000_000 and not args.no_secondary):
+    if (args.full and line is not None and world == 1 and not force_sharded and args.config == "c2" and int(args.reads) == 100_000_000 and not args.no_secondary):
         try:
             line["secondary"]["bam_ingest"] = measure_bam_ingest()
         except Exception as e:

@@ -3,7 +3,7 @@
 # it prints to keep goes to gpurun_out/.  Usage:  bash scripts/gpu_job.sh <word> [args...]   (several jobs: separate them with ---)
 #   tests <pytest args>             python -m pytest -m gpu -x -q <args>         -> gpurun_out/tests_<n>.log
 #   bench <name> <bench.py args>    python bench.py <args>                       -> gpurun_out/bench_<name>.json (+ a summary line on stdout)
-#   stages <name> <bench.py args>   the same, printing the host stages and kernels of the line sorted by time
+#   stages <name> <bench.py args>   the same with --full, printing the host stages and kernels of the line sorted by time
 #   prof <tag>                      scripts/refresh_profiles.sh <tag>
 #   py <script> [args]              python <script> [args]                       -> gpurun_out/py_<n>.log
 cd "${GRAFT_REPO_ROOT:-/root/repo}" || exit 1
@@ -17,6 +17,7 @@ run_one() {
     tests) timeout 3000 python -m pytest -m gpu -x -q "$@" > gpurun_out/tests_$n.log 2>&1; echo "tests_$n rc $? : $(tail -1 gpurun_out/tests_$n.log)";;
     bench|stages)
       local name=$1; shift
+      [ "$word" = stages ] && set -- --full "$@"
       timeout 1500 python bench.py "$@" 2> gpurun_out/bench_$name.err | tail -1 > gpurun_out/bench_$name.json
       python - "$name" "$word" <<'PY'
 import json, sys

@@ -1,5 +1,5 @@
 """N plain passes of the bench's C2 (or c3) workload and nothing else -- the command to put under rocprofv3 --kernel-trace for
-scripts/trace_gaps.py (bench.py itself runs a kernel-table pass, the other matrix forms and the ingest legs after its timed region).
+scripts/trace_gaps.py (bench.py --full itself runs a kernel-table pass, the other matrix forms and the ingest legs after its timed region).
 usage: plain_passes.py [config] [reads] [passes]"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -5,7 +5,7 @@
 cd "${GRAFT_REPO_ROOT:-/root/repo}" || exit 1
 export PYTHONPATH=$PWD
 OUT=gpurun_out/${TAG:-r06c}; T=${TAG:-r06c}; mkdir -p $OUT
-timeout 1200 python bench.py --steps 20 --warmup 5 2> $OUT/bench.err | head -1 > $OUT/${T}_bench_c2.json
+timeout 1200 python bench.py --full --steps 20 --warmup 5 2> $OUT/bench.err | head -1 > $OUT/${T}_bench_c2.json
 bash scripts/r06_bam_breakdown.sh > $OUT/breakdown.log 2>&1
 for k in real:3x easy:10x; do a=${k%%:*}; b=${k#*:}; cp gpurun_out/bam_r06/${a}_device_trace.txt $OUT/${T}_bam_${b}_file_device_trace.txt; cp gpurun_out/bam_r06/${a}_ingest.jsonl $OUT/${T}_bam_${b}_file_ingest.jsonl; cp gpurun_out/bam_r06/${a}_kernel_stats.csv $OUT/${T}_bam_${b}_file_kernel_stats.csv 2>/dev/null; done
 { REAL=1 timeout 300 python scripts/bench_bgzf_inflate.py 300000 40 2>&1 | tail -1; timeout 300 python scripts/bench_bgzf_inflate.py 300000 40 2>&1 | tail -1; REAL=1 DROPEST_INFLATE_PAR=0 timeout 300 python scripts/bench_bgzf_inflate.py 300000 40 2>&1 | tail -1; DROPEST_INFLATE_PAR=0 timeout 300 python scripts/bench_bgzf_inflate.py 300000 40 2>&1 | tail -1; } > $OUT/${T}_bgzf_inflate.jsonl

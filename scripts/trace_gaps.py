@@ -1,5 +1,5 @@
 """Idle time of the device inside one pass: from a rocprofv3 --kernel-trace CSV (kernel start / end timestamps) of a bench run, the gaps
-between consecutive kernels of one pass (TRACE_PASS: 0-based from the start, negative from the end, default the last one; bench.py --steps 2 --warmup 1
+between consecutive kernels of one pass (TRACE_PASS: 0-based from the start, negative from the end, default the last one; bench.py --steps 2 --warmup 1 --full
 runs the warm-up, two timed steps, then table steps with HIP events around every launch and the other matrix forms: 2 is the second timed step), largest first, with the
 kernels on either side.  usage: trace_gaps.py <dir with *kernel_trace.csv> [how many of the pass's last kernels to list on a time line]"""
 import csv, glob, os, sys

@@ -34,7 +34,7 @@ def _line(res):
 
 
 def test_two_ranks_on_one_gpu_print_the_line_of_one_rank(tmp_path):
-    common = ["--steps", "2", "--warmup", "1", "--cpu-sample", "0", "--push-sample", "0", "--no-secondary"]
+    common = ["--steps", "2", "--warmup", "1", "--full", "--cpu-sample", "0", "--push-sample", "0", "--no-secondary"]
     env = dict(os.environ, PYTHONPATH=ROOT, DROPEST_BENCH_NO_BAM="1", DROPEST_BENCH_NO_FORMS="1")
     one = tmp_path / "one.npz"
     r1 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--reads", "2000000", "--cells", "400", "--dump-matrices", str(one)] + common,
