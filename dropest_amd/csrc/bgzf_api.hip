@@ -30,6 +30,27 @@ template <class F> int bgzf_guarded(F &&f) {
 
 extern "C" const char *dropest_bgzf_last_error(void) { return g_bgzf_error.c_str(); }
 
+// The parallel inflate's scratch per (device, stream): a block counter and the waves' match lists (~0.5 GB).  Entries of a decoder's streams are
+// given back when the decoder lets go of the stream (bgzf_release_inflate_scratch); the null stream's entry stays for the process.
+namespace {
+struct InflateScratch { DevBuf<InfpMatch> list; DevBuf<uint32_t> next; uint32_t grid = 0; };
+std::mutex g_inflate_scratch_mu;
+std::map<std::pair<int, void *>, std::unique_ptr<InflateScratch>> g_inflate_scratch;
+
+// freed after the work already queued on `stream` (which may still use the scratch) is done
+void bgzf_release_inflate_scratch(int device, void *stream) {
+	std::unique_ptr<InflateScratch> gone;
+	{
+		std::lock_guard<std::mutex> lk(g_inflate_scratch_mu);
+		auto it = g_inflate_scratch.find({device, stream});
+		if (it == g_inflate_scratch.end()) return;
+		gone = std::move(it->second);
+		g_inflate_scratch.erase(it);
+	}
+	(void)hipStreamSynchronize(hipStream_t(stream));
+}
+}  // namespace
+
 extern "C" int dropest_bgzf_scan(const uint8_t *data, uint64_t len, uint64_t cap, uint64_t *in_off, uint32_t *in_len, uint64_t *out_off,
                                  uint32_t *out_len, uint32_t *crc32, uint64_t *n_blocks, uint64_t *bytes_used, uint64_t *out_total) {
 	return bgzf_guarded([&] {
@@ -77,24 +98,20 @@ extern "C" int dropest_bgzf_inflate_device(int device, void *stream, const uint8
 		static const int par = [] { const char *e = getenv("DROPEST_INFLATE_PAR"); return e ? atoi(e) : 1; }();
 		if (par) {
 			// the lanes of a wave on different parts of a block's symbol stream (k_inflate_par.h); the waves take blocks from a counter and keep their
-			// match lists in a scratch buffer of the (device, stream) they run on
-			struct Scratch { DevBuf<InfpMatch> list; DevBuf<uint32_t> next; uint32_t grid = 0; };
-			static std::mutex mu;
-			static std::map<std::pair<int, void *>, std::unique_ptr<Scratch>> pool;
-			Scratch *sc = nullptr;
-			{
-				std::lock_guard<std::mutex> lk(mu);
-				auto &slot = pool[{device, stream}];
-				if (!slot) {
-					slot.reset(new Scratch());
-					hipDeviceProp_t prop{};
-					HIP_CHECK(hipGetDeviceProperties(&prop, device));
-					slot->grid = uint32_t(prop.multiProcessorCount) * 4u;
-					slot->list.alloc(size_t(slot->grid) * INFP_WAVES * INFP_MATCH_CAP);
-					slot->next.alloc(1);
-				}
-				sc = slot.get();
+			// match lists in a scratch buffer of the (device, stream) they run on.  The pool's lock is held from the counter's reset to the launch: two
+			// calls on one stream then enqueue (memset, kernel) pairs that the stream orders one after the other, never memset A, memset B, kernel A,
+			// kernel B (kernel B would find the counter past its blocks and inflate none)
+			std::lock_guard<std::mutex> lk(g_inflate_scratch_mu);
+			auto &slot = g_inflate_scratch[{device, stream}];
+			if (!slot) {
+				slot.reset(new InflateScratch());
+				hipDeviceProp_t prop{};
+				HIP_CHECK(hipGetDeviceProperties(&prop, device));
+				slot->grid = uint32_t(prop.multiProcessorCount) * 4u;
+				slot->list.alloc(size_t(slot->grid) * INFP_WAVES * INFP_MATCH_CAP);
+				slot->next.alloc(1);
 			}
+			InflateScratch *const sc = slot.get();
 			HIP_CHECK(hipMemsetAsync(sc->next.p, 0, 4, hipStream_t(stream)));
 			// (DROPEST_INFLATE_PAR_WGS_PER_CU=1..3: fewer workgroups than the CUs hold, so that kernels of other streams find wave slots and LDS beside this one)
 			static const uint32_t wgs_per_cu = [] { const char *e = getenv("DROPEST_INFLATE_PAR_WGS_PER_CU"); const int v = e ? atoi(e) : 4; return uint32_t(v < 1 ? 1 : v > 4 ? 4 : v); }();
@@ -223,7 +240,7 @@ struct dropest_bam_decoder {
 	DevBuf<uint32_t> a_pos, a_end, a_gene;
 	dropest_annotation *annotation = nullptr;   // -g: not owned
 	uint32_t n_ann_genes = 0;
-	DevBuf<uint16_t> o_uql;
+	DevBuf<uint32_t> o_uql;
 	DevBuf<uint8_t> o_status, o_need;
 	DevBuf<BamWindowCounts> d_wc;
 	PinnedBuf<uint8_t> h_stage[2];
@@ -535,6 +552,7 @@ extern "C" int dropest_bam_decoder_use_stream(dropest_bam_decoder *d, void *stre
 			std::fprintf(stderr, "[bam] use_stream: the kernels' stream waited for %.1f ms\n", std::chrono::duration<double, std::milli>(clk::now() - t0).count());
 		}
 		if (d->stream) HIP_CHECK(hipStreamSynchronize(d->stream));
+		if (d->stream && d->stream != hipStream_t(stream)) bgzf_release_inflate_scratch(d->device, d->stream);      // (a stream let go of keeps no scratch of the decoder's)
 		d->stream = stream ? hipStream_t(stream) : d->own_stream;      // (null: bam_ready makes the decoder's own)
 	});
 }
@@ -545,6 +563,10 @@ extern "C" void dropest_bam_decoder_destroy(dropest_bam_decoder *d) {
 	(void)hipStreamSynchronize(d->up_stream);
 	for (hipEvent_t e : d->up_done) if (e) (void)hipEventDestroy(e);
 	for (hipEvent_t e : d->piece_done) if (e) (void)hipEventDestroy(e);
+	// the inflate scratch of every stream the decoder inflated on (a lent one it still holds, its own, its fronts')
+	if (d->stream && d->stream != d->own_stream) bgzf_release_inflate_scratch(d->device, d->stream);
+	if (d->own_stream) bgzf_release_inflate_scratch(d->device, d->own_stream);
+	for (BamFront &f : d->front) if (f.stream) bgzf_release_inflate_scratch(d->device, f.stream);
 	if (d->own_stream) { (void)hipStreamSynchronize(d->own_stream); (void)hipStreamDestroy(d->own_stream); }
 	for (BamFront &f : d->front) if (f.stream) { (void)hipStreamSynchronize(f.stream); (void)hipStreamDestroy(f.stream); }
 	delete d;
@@ -743,6 +765,8 @@ extern "C" int dropest_bam_decoder_window_inflate(dropest_bam_decoder *dec, cons
 				HIP_CHECK(hipGetLastError());
 			}
 			d->ms_copy = ms_since(t0);
+			// (every verdict "not inflated" until the kernel says otherwise: a block it never reaches goes to the host fall-back, not through with stale bytes)
+			HIP_CHECK(hipMemsetAsync(d->d_status.p, 0xFF, size_t(n) * 4, st));
 			if (dropest_bgzf_inflate_device(dec->device, st, uploaded ? uploaded : d->d_in.p, len, d->d_in_off.p, d->d_in_len.p, d->d_out_off.p, d->d_out_len.p, uint32_t(n), d->d_out.p + d->reserve, d->d_status.p, d->d_crc.p))
 				throw DeviceError(g_bgzf_error);
 			hipLaunchKernelGGL(bam_words_to_host_kernel, dim3(uint32_t((n + 255) / 256)), dim3(256), 0, st, d->d_status.p, d->h_block_status.p, uint32_t(n));
@@ -939,7 +963,7 @@ extern "C" int dropest_bam_decoder_window_finish(dropest_bam_decoder *d, int slo
 		HIP_CHECK(hipStreamSynchronize(st));
 		lap("kernels done");
 		if (n_rec) { std::memcpy(&wc, d->h_result.p, sizeof(wc)); totals[0] = d->h_result.p[10]; totals[1] = d->h_result.p[11]; bad_record = d->h_result.p[12]; }
-		if (bad_record) throw InvalidError("Corrupt BAM record");      // (a block_size below the 32 bytes of a record's fixed part or beyond 2^26, met by the walk from the checked starts; fixed part + name + cigar + bases longer than the record, met by the parse)
+		if (bad_record) throw InvalidError("Corrupt BAM record");      // (a block_size below the 32 bytes of a record's fixed part, met by the walk from the checked starts; fixed part + name + cigar + bases longer than the record, met by the parse)
 		const uint32_t n_need = totals[1];
 		if (n_need) {
 			d->h_need_rec.ensure(n_need); d->h_need_pos.ensure(n_need); d->h_need_size.ensure(n_need);

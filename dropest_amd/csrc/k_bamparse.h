@@ -89,7 +89,8 @@ __global__ __launch_bounds__(256) void bam_seg_guess_kernel(const uint8_t *__res
 
 // A lane per listed segment walks the records that START in it, from seg_start: count[k] of them (their offsets to rec_off + base[k]
 // when rec_off is given), seg_exit[k] = where the chain stands afterwards (the first start at or beyond the segment's end, or the start
-// of the record the data cuts off).  bad[0] is raised by a record shorter than its fixed part or longer than 2^26 bytes.
+// of the record the data cuts off).  bad[0] is raised by a record shorter than its fixed part.  (A record of any longer block_size is walked over as
+// the host reader walks it, bam_ingest.cpp BamReader::next: the cap of bam_plausible is for guesses only, and the host's check repairs those.)
 __global__ __launch_bounds__(256) void bam_seg_walk_kernel(const uint8_t *__restrict__ d, uint64_t len, const uint32_t *__restrict__ list, uint32_t n_list,
                                                            const uint64_t *__restrict__ seg_start, uint32_t *__restrict__ count, uint64_t *__restrict__ seg_exit,
                                                            const uint32_t *__restrict__ base, uint64_t *__restrict__ rec_off, uint32_t *__restrict__ bad) {
@@ -102,7 +103,7 @@ __global__ __launch_bounds__(256) void bam_seg_walk_kernel(const uint8_t *__rest
 	if (o == BAM_NONE) { count[k] = 0; seg_exit[k] = BAM_NONE; return; }
 	while (o < end && o + 4 <= len) {
 		const uint32_t bs = b_le32(d + o);
-		if (bs < 32u || bs > (1u << 26)) { atomicOr(bad, 1u); break; }   // (beyond any record, as bam_plausible has it: garbage must not become a tail carried from window to window)
+		if (bs < 32u) { atomicOr(bad, 1u); break; }
 		if (o + 4ull + bs > len) break;                // cut off by the end of the window: the tail of the next one
 		if (rec_off) rec_off[base[k] + c] = o;
 		++c;
@@ -118,7 +119,7 @@ __global__ __launch_bounds__(256) void bam_seg_walk_kernel(const uint8_t *__rest
 struct BamRecordOut {
 	unsigned long long *cb, *umi;
 	uint32_t *gene, *aux;
-	uint16_t *umiq_len;
+	uint32_t *umiq_len;           // the true length (quality_len_min / _max of a window report it)
 	unsigned long long *qoff;     // where the record's UMI quality string stands in the window (~0: it has none)
 	uint8_t *status, *need;
 	// -g (genes from a GTF / BED annotation, ReadParamsParser::get_gene_from_reference :92-151): the record's chromosome in the annotation's
@@ -256,7 +257,7 @@ __global__ __launch_bounds__(BAM_PARSE_T) void bam_parse_kernel(const uint8_t *_
 			if (found[T_CBQ]) for (uint32_t j = 0; j < vlen[T_CBQ]; ++j) pass &= int32_t(int8_t(val[T_CBQ][j])) >= int32_t(int8_t(cfg.min_phred));
 			if (found[T_UMIQ]) for (uint32_t j = 0; j < vlen[T_UMIQ]; ++j) pass &= int32_t(int8_t(val[T_UMIQ][j])) >= int32_t(int8_t(cfg.min_phred));
 		}
-		out.umiq_len[i] = uint16_t(found[T_UMIQ] ? (vlen[T_UMIQ] > 0xFFFFu ? 0xFFFFu : vlen[T_UMIQ]) : 0u);
+		out.umiq_len[i] = found[T_UMIQ] ? vlen[T_UMIQ] : 0u;
 		if (found[T_UMIQ]) out.qoff[i] = my_off + uint64_t(val[T_UMIQ] - at);
 	} else {                                                                  // ReadParamsParser.cpp:20-33: "id!CB#UMI"
 		const uint8_t *name = p + 32;
@@ -370,7 +371,7 @@ constexpr uint32_t BAM_FIN_PER = 16, BAM_FIN_TILE = 256 * BAM_FIN_PER;
 struct BamWindowCounts { uint32_t status[5]; uint32_t quality, any_gene, ql_max, ql_min_inv, pad; };
 
 // accepted records and accepted records the host must see, per tile of 4 096 records; the window's counters
-__global__ __launch_bounds__(256) void bam_fin_count_kernel(const uint8_t *__restrict__ status, const uint8_t *__restrict__ need, const uint16_t *__restrict__ uql,
+__global__ __launch_bounds__(256) void bam_fin_count_kernel(const uint8_t *__restrict__ status, const uint8_t *__restrict__ need, const uint32_t *__restrict__ uql,
                                                             uint32_t n, uint32_t *__restrict__ tile_ok, uint32_t *__restrict__ tile_need, BamWindowCounts *__restrict__ wc) {
 	__shared__ uint32_t acc[10];
 	if (threadIdx.x < 10) acc[threadIdx.x] = 0;

@@ -69,7 +69,7 @@ typedef struct dropest_bam_window {        /* host pointers: pinned memory of th
 	uint32_t n_blocks, refused_blocks;     /* blocks the device left to `inflate_fallback` */
 	uint32_t guesses_repaired, pad;        /* segments whose guessed first record was not on the chain (walked again from the true place) */
 	double ms_inflate, ms_boundaries, ms_parse, ms_copy;
-	uint32_t quality_len_min, quality_len_max;   /* shortest / longest UMI quality string over the accepted GENE-BEARING reads (0 = none) */
+	uint32_t quality_len_min, quality_len_max;   /* shortest / longest UMI quality string over the accepted GENE-BEARING reads, true lengths (0 = none) */
 } dropest_bam_window;
 
 /* raw DEFLATE of one block on the host (zlib or the like) for the blocks the device refuses; 0 = ok */

@@ -1,0 +1,248 @@
+"""What one BAM record becomes on the way into the Estimation path, restated in plain Python: TEST INFRASTRUCTURE for the device decoder
+(include/dropest_bgzf.h, dropest_bam_decoder_*) and the host reader (dropest_amd/csrc/host/bam_ingest.cpp).  Written from the rules of the
+host reader (parse_one, BamRecord::get_string_tags) and of the reference they restate -- BamController.cpp:85-172, FilledBamParamsParser.cpp:12-40,
+ReadParamsParser.cpp:20-90, ReadParameters.cpp:118-136 -- not from the kernel.
+
+  parse_record(rec, cfg, dicts) -> Row: the reader's status, and for an accepted record the four columns of dropest_push_reads
+  (cb, umi, gene, aux), the `need` bits and the UMI quality string.
+  window(rows) -> the per-window summary the decoder reports (counts, quality_seen, any_gene, quality_len_min / _max, the need list)."""
+import struct
+from dataclasses import dataclass, field
+
+OK, SKIP, CANT_PARSE_NO_COUNT, CANT_PARSE, LOW_QUALITY = range(5)      # DROPEST_BAM_* (include/dropest_bgzf.h)
+NO_GENE = 0xFFFFFFFF
+QUALITY_OFFSET = 33                                                    # Tools::ReadParameters::quality_offset
+HAS_NOT_ANNOTATED, HAS_EXONS, HAS_INTRONS = 1, 2, 4                    # UMI::Mark bits
+T_CB, T_UMI, T_CBQ, T_UMIQ, T_GENE, T_TYPE = range(6)                  # the order of dropest_bam_parse_cfg.tag
+
+
+@dataclass
+class Cfg:
+    """dropest_bam_parse_cfg in Python terms: tags as two-letter strings ("" = not asked)."""
+    tags: tuple = ("CB", "UB", "", "", "GX", "")
+    filled_bam: bool = True
+    min_phred: int = 0
+    read_type: bool = False              # has_read_type: a read-type tag is configured
+    intronic: bytes = b""
+    intergenic: bytes = b""
+    n_refs: int = 1
+
+
+@dataclass
+class Dicts:
+    """The decoder's copy of the caller's dictionaries: gene hash (masked) -> gene id (the first pair with a hash keeps it), reference -> chromosome
+    index (-1 = none yet), optionally the gene names by id (then a hash that is found must also name the same bytes)."""
+    genes: dict = field(default_factory=dict)
+    chr_of_ref: list = field(default_factory=list)
+    names: list = None
+    hash_mask: int = (1 << 64) - 1
+
+
+@dataclass
+class Row:
+    status: int
+    cb: int = 0
+    umi: int = 0
+    gene: int = 0
+    aux: int = 0
+    need: int = 0                        # bit 0: the caller must see the record's bytes; bit 1: it carries a gene name
+    umi_quality: bytes = None            # the UMI quality string (-f with the tag present), else None
+    size: int = 0                        # 4 + block_size
+    strings: tuple = None                # accepted: (barcode, UMI, gene name, ref_id, mark) as the container's add_record would take them
+
+
+def fnv1a(b):                            # CellsDataContainer::hash_name (host/facade.cpp)
+    h = 1469598103934665603
+    for c in b:
+        h = ((h ^ c) * 1099511628211) & 0xFFFFFFFFFFFFFFFF
+    return h
+
+
+def tag16(t):
+    return ord(t[0]) | (ord(t[1]) << 8) if t else 0
+
+
+def pack(s):
+    """CellsDataContainer::pack_code: 1..31 bases of A C G T -> 1 followed by two bits a base; anything else (N, lowercase, bytes >= 0x80, empty,
+    32 bases or more) -> 0, and the caller packs or interns the string itself."""
+    if not 1 <= len(s) <= 31:
+        return 0
+    c = 1
+    for ch in s:
+        k = b"ACGT".find(bytes([ch]))
+        if k < 0:
+            return 0
+        c = (c << 2) | k
+    return c
+
+
+_WIDTH = {ord("A"): 1, ord("c"): 1, ord("C"): 1, ord("s"): 2, ord("S"): 2, ord("i"): 4, ord("I"): 4, ord("f"): 4}
+
+
+def string_tags(tags, wanted):
+    """BamRecord::get_string_tags (host/bam_ingest.cpp:571-610): one walk over the aux bytes.  Returns {k: value bytes} for the wanted names.
+    - the first occurrence of a name wins;
+    - Z and H are strings up to their NUL; A counts as a string of one byte;
+    - any numeric occurrence (c C s S i I f, B) "closes" the name: later occurrences of it are not looked at;
+    - an unknown type, a string without its NUL or a value that runs past the end stops the walk: later tags are not seen."""
+    found, closed = {}, set()
+    o, n = 0, len(tags)
+    while o + 3 <= n:
+        name, typ = tags[o] | (tags[o + 1] << 8), tags[o + 2]
+        o += 3
+        text = False
+        if typ in _WIDTH:
+            ln = _WIDTH[typ]
+        elif typ in (ord("Z"), ord("H")):
+            e = tags.find(b"\0", o)
+            if e < 0:
+                return found
+            ln, text = e - o + 1, True
+        elif typ == ord("B"):
+            if o + 5 > n:
+                return found
+            sub = tags[o]
+            w = 1 if sub in b"cC" else 2 if sub in b"sS" else 4      # (any other subtype is taken as four bytes wide, as both readers do)
+            ln = 5 + struct.unpack_from("<I", tags, o + 1)[0] * w
+        else:
+            return found
+        if o + ln > n:
+            return found
+        for k, want in enumerate(wanted):
+            if not want or want != name or k in found or k in closed:
+                continue
+            if text:
+                found[k] = bytes(tags[o:o + ln - 1])
+            elif typ == ord("A"):
+                found[k] = bytes(tags[o:o + 1])
+            else:
+                closed.add(k)
+        o += ln
+    return found
+
+
+def parse_record(rec, cfg, dicts):
+    """One record (its bytes, block_size field first) -> Row.  Raises ValueError where both readers call the record corrupt."""
+    block_size, ref_id, _pos, l_read_name, _mapq, _bin, n_cigar, flag, l_seq = struct.unpack_from("<IiiBBHHHI", rec, 0)
+    if block_size < 32 or len(rec) != 4 + block_size:
+        raise ValueError("Corrupt BAM record")
+    aux = 32 + l_read_name + 4 * n_cigar + (l_seq + 1) // 2 + l_seq
+    if aux > block_size:                                                  # bam_ingest.cpp parse_record: "Corrupt BAM record"
+        raise ValueError("Corrupt BAM record")
+    size = 4 + block_size
+    if flag & 0x4 or flag & 0x100:                                        # BamController.cpp:87-88: unmapped or not primary (0x800 is NOT skipped)
+        return Row(SKIP, size=size)
+    if ref_id < 0 or ref_id >= cfg.n_refs:                                # :90-104 (ref_id == n_refs included)
+        return Row(CANT_PARSE_NO_COUNT, size=size)
+    tv = string_tags(rec[4 + aux:], [tag16(t) for t in cfg.tags])
+    uq = None
+    if cfg.filled_bam:                                                    # FilledBamParamsParser.cpp:12-40
+        if T_CB not in tv or T_UMI not in tv:
+            return Row(CANT_PARSE, size=size)
+        cb, umi = tv[T_CB], tv[T_UMI]
+        if not cb or not umi:                                             # the ReadParameters constructor throws on an empty barcode / UMI
+            return Row(CANT_PARSE, size=size)
+        uq = tv.get(T_UMIQ)
+        if cfg.min_phred > QUALITY_OFFSET:                                # ReadParameters.cpp:118-136: every byte >= min, compared as signed char
+            lim = (cfg.min_phred & 0xFF) - (256 if cfg.min_phred & 0x80 else 0)
+            sc = lambda b: b - 256 if b >= 0x80 else b
+            if any(sc(q) < lim for q in tv.get(T_CBQ, b"") + (uq or b"")):
+                return Row(LOW_QUALITY, size=size)
+    else:                                                                 # ReadParamsParser.cpp:20-33: "id!CB#UMI", no quality filter
+        name = rec[36:36 + max(l_read_name - 1, 0)]
+        up = name.rfind(b"#")
+        cp = name.rfind(b"!", 0, up + 1) if up >= 0 else -1               # rfind('!', up): at or before the '#'
+        if up < 0 or cp < 0:
+            return Row(CANT_PARSE, size=size)
+        cb, umi = name[cp + 1:up], name[up + 1:]
+        if not cb or not umi:
+            return Row(CANT_PARSE, size=size)
+    # get_gene + parse_read_type (ReadParamsParser.cpp:36-90)
+    if T_GENE not in tv:
+        mark = HAS_NOT_ANNOTATED
+    elif not cfg.read_type or T_TYPE not in tv:
+        mark = HAS_EXONS
+    elif tv[T_TYPE] == cfg.intronic:
+        mark = HAS_INTRONS
+    elif cfg.intergenic and tv[T_TYPE] == cfg.intergenic:                # an intergenic value that is not configured matches nothing
+        mark = HAS_NOT_ANNOTATED
+    else:
+        mark = HAS_EXONS
+    gname = tv.get(T_GENE, b"")
+    has_gene = len(gname) > 0                                             # an empty gene name is no gene
+    # the columns as fast_window (host/bam_ingest.cpp) fills them; 0 / need where the dictionaries cannot answer
+    need = False
+    cbc = pack(cb)
+    need |= cbc == 0
+    umic, gid = 1, NO_GENE
+    if has_gene:
+        umic = pack(umi)
+        need |= umic == 0
+        h = fnv1a(gname) & dicts.hash_mask
+        if h not in dicts.genes:
+            need, gid = True, 0
+        else:
+            gid = dicts.genes[h]
+            if not need and dicts.names is not None and (gid >= len(dicts.names) or dicts.names[gid] != gname):
+                need, gid = True, 0                                       # a name that only shares the hash (StringIndexer keys by the bytes)
+    aux_w = mark << 16
+    if not has_gene or mark & (HAS_EXONS | HAS_INTRONS):                  # the read reaches Stats::inc(chromosome)
+        c = dicts.chr_of_ref[ref_id] if ref_id < len(dicts.chr_of_ref) else -1
+        if c < 0:
+            need = True
+        else:
+            aux_w |= c
+    return Row(OK, cbc, umic, gid, aux_w, (1 if need else 0) | (2 if has_gene else 0), uq if cfg.filled_bam else None, size,
+               (bytes(cb), bytes(umi), gname, ref_id, mark))
+
+
+@dataclass
+class WindowSummary:
+    counts: list
+    n_accepted: int
+    need_rec: list
+    need_pos: list
+    need_size: list
+    quality_seen: int
+    any_gene: int
+    quality_len_min: int
+    quality_len_max: int
+
+
+def window(rows):
+    """The decoder's report of one window from the rows of the records that start in it (in file order): counts per status, the accepted
+    records the caller must see (index in the window, row in the dense columns, bytes), whether any accepted record has a non-empty UMI
+    quality string or a gene, and the shortest / longest UMI quality string over the accepted gene-bearing records (their TRUE lengths)."""
+    counts = [0] * 5
+    need_rec, need_pos, need_size, qls = [], [], [], []
+    quality_seen = any_gene = 0
+    at = 0
+    for i, r in enumerate(rows):
+        counts[r.status] += 1
+        if r.status != OK:
+            continue
+        if r.need & 1:
+            need_rec.append(i); need_pos.append(at); need_size.append(r.size)
+        quality_seen |= int(bool(r.umi_quality))
+        if r.need & 2:
+            any_gene = 1
+            qls.append(len(r.umi_quality or b""))
+        at += 1
+    return WindowSummary(counts, at, need_rec, need_pos, need_size, quality_seen, any_gene, min(qls) if qls else 0, max(qls) if qls else 0)
+
+
+def records_of(raw):
+    """The BAM stream after BGZF (header included) -> (offset of the first record, [record bytes, ...]).  A pure-Python walk of SAMv1 §4.2."""
+    assert raw[:4] == b"BAM\x01"
+    o = 8 + struct.unpack_from("<I", raw, 4)[0]
+    n_ref = struct.unpack_from("<I", raw, o)[0]
+    o += 4
+    for _ in range(n_ref):
+        o += 8 + struct.unpack_from("<I", raw, o)[0]
+    first, recs = o, []
+    while o < len(raw):
+        bs = struct.unpack_from("<I", raw, o)[0]
+        recs.append(raw[o:o + 4 + bs])
+        o += 4 + bs
+    assert o == len(raw)
+    return first, recs

@@ -1,5 +1,6 @@
 """Minimal BAM writer (SAMv1 §4: BGZF container + BAM records), TEST INFRASTRUCTURE for the native BAM reader
-(dropest_amd/csrc/host/bam_ingest.cpp).  Records may straddle BGZF blocks (the byte stream is cut at a fixed size)."""
+(dropest_amd/csrc/host/bam_ingest.cpp) and the device decoder.  Records may straddle BGZF blocks (the byte stream is cut at `block` bytes,
+chosen per file)."""
 import struct
 import zlib
 
@@ -14,36 +15,45 @@ def _bgzf_block(data, level=6):
             + cdata + struct.pack("<II", zlib.crc32(data) & 0xFFFFFFFF, len(data)))
 
 
-def _tag(tag, typ, value):
+_B_SUB = {"c": "b", "C": "B", "s": "h", "S": "H", "i": "i", "I": "I", "f": "f"}     # B array subtype -> struct code (SAMv1 §4.2.4)
+_NUM = {"c": "<b", "C": "<B", "s": "<h", "S": "<H", "i": "<i", "I": "<I", "f": "<f"}
+
+
+def _tag(tag, typ=None, value=None):
+    """(tag, type, value) -> the bytes of one aux field.  Z / H: a string (NUL added); A: one character; c C s S i I f: a number;
+    B: a list of int16, or (subtype, list) for any of the seven subtypes.  A bare bytes object is written as it stands (unknown types,
+    values cut short: whatever a test needs)."""
+    if isinstance(tag, (bytes, bytearray)):
+        return bytes(tag)
     t = tag.encode() + typ.encode()
-    if typ == "Z":
-        return t + value.encode() + b"\x00"
+    if typ in ("Z", "H"):
+        return t + (value if isinstance(value, bytes) else value.encode()) + b"\x00"
     if typ == "A":
-        return t + value.encode()[:1]
-    if typ == "i":
-        return t + struct.pack("<i", value)
-    if typ == "C":
-        return t + struct.pack("<B", value)
-    if typ == "f":
-        return t + struct.pack("<f", value)
-    if typ == "B":                     # value = list of int16
-        return t + b"s" + struct.pack("<I", len(value)) + struct.pack("<%dh" % len(value), *value)
+        return t + (value if isinstance(value, bytes) else value.encode())[:1]
+    if typ in _NUM:
+        return t + struct.pack(_NUM[typ], value)
+    if typ == "B":                     # value = list of int16, or (subtype, list)
+        sub, vals = value if isinstance(value, tuple) else ("s", value)
+        return t + sub.encode() + struct.pack("<I", len(vals)) + struct.pack("<%d%s" % (len(vals), _B_SUB[sub]), *vals)
     raise ValueError(typ)
 
 
 _CIGAR = {c: i for i, c in enumerate("MIDNSHP=X")}
 
 
-def record(ref_id, pos, name, flag=0, mapq=255, seq="ACGT" * 10, tags=(), cigar=None):
-    """cigar: list of (length, op) -- default one M over the whole read"""
+def record(ref_id, pos, name, flag=0, mapq=255, seq="ACGT" * 10, tags=(), cigar=None, qual=None, next_ref=-1, next_pos=-1, l_read_name=None):
+    """cigar: list of (length, op) -- default one M over the whole read (an empty list: no CIGAR at all).  name: str or bytes (NUL added).
+    qual: the quality bytes (default 0xFF each).  l_read_name: the field as written, whatever the name's length (the record's bytes stay
+    as they are: block_size counts them).  tags: (tag, type, value) triples or raw bytes (see _tag)."""
     n = len(seq)
-    ops = cigar or [(n, "M")]
-    cigar = b"".join(struct.pack("<I", (ln << 4) | _CIGAR[op]) for ln, op in ops)
+    ops = [(n, "M")] if cigar is None else cigar
+    cigar = b"".join(struct.pack("<I", (ln << 4) | (_CIGAR[op] if isinstance(op, str) else op)) for ln, op in ops)
     packed = bytearray((n + 1) // 2)
     for i, c in enumerate(seq):
         packed[i // 2] |= _SEQ[c] << (4 if i % 2 == 0 else 0)
-    body = struct.pack("<iiBBHHHIiii", ref_id, pos, len(name) + 1, mapq, 4680, len(ops), flag, n, -1, -1, 0)
-    body += name.encode() + b"\x00" + cigar + bytes(packed) + b"\xff" * n + b"".join(_tag(*t) for t in tags)
+    nm = (name if isinstance(name, bytes) else name.encode()) + b"\x00"
+    body = struct.pack("<iiBBHHHIiii", ref_id, pos, len(nm) if l_read_name is None else l_read_name, mapq, 4680, len(ops), flag, n, next_ref, next_pos, 0)
+    body += nm + cigar + bytes(packed) + (b"\xff" * n if qual is None else bytes(qual)) + b"".join(_tag(*t) if isinstance(t, tuple) else _tag(t) for t in tags)
     return struct.pack("<I", len(body)) + body
 
 
