@@ -219,8 +219,8 @@ def set_dicts(L, dec, dicts, pairs, names):
 
 class BamFile:
     """A written file: its compressed blocks from the one that holds the first record on, the inflated stream, the records and where they end."""
-    def __init__(self, path, recs, block):
-        bw.write_bam(path, REFS, recs, block=block)
+    def __init__(self, path, recs, block, compress=None):
+        bw.write_bam(path, REFS, recs, block=block, compress=compress)
         self.blob = open(path, "rb").read()
         raw = gzip.decompress(self.blob)
         first, got = bm.records_of(raw)
