@@ -33,8 +33,9 @@ const char *dropest_annotation_last_error(void);
 /* n reads given as host arrays: chromosome index into the annotation's chromosome list (-1 = unknown name),
  * alignment start and end (BamAlignment::Position / GetEndPosition).  Per read: gene index or 0xFFFFFFFF, and the
  * UMI::Mark bits (1 not annotated, 2 exon, 4 intron), -1 for an unknown chromosome
- * (RefGenesContainer::ChrNotFoundException), -2 when more than 16 (gene, type) results met at one end point (the
- * caller resolves those on the host). */
+ * (RefGenesContainer::ChrNotFoundException), -2 when more than 16 distinct transcripts cover one of the two end
+ * points -- however few (gene, type) results they give: 17 isoforms of one gene are enough -- or more than 16
+ * (gene, type) results meet there (the caller resolves those on the host; gene is 0xFFFFFFFF then). */
 int dropest_annotation_query(dropest_annotation *a, uint64_t n, const int32_t *chr, const uint32_t *position,
                              const uint32_t *end_position, uint32_t *gene, int32_t *mark);
 

@@ -105,3 +105,133 @@ def test_device_annotation_on_random_annotations(tmp_path, seed, with_introns):
     with gzip.open(path, "wt") as f:
         f.write("\n".join(lines) + "\n")
     assert _check(path, ["chr1", "chr2", "chrX", "chrNope"], 0, 95_000, 30_000, seed) > 3000
+
+
+# ---- generated files (annotation_cases.py): every query against the oracle and, on simple files, the model (annotation_model.py) ----
+import annotation_cases as ac
+
+CAP = 16      # ANN_CAP of csrc/annotation_api.hip
+
+
+@pytest.fixture(scope="module")
+def cases(tmp_path_factory):
+    d = tmp_path_factory.mktemp("annotation_cases")
+    return {s: ac.make(d, s) for s in ac.STREAMS}
+
+
+def _raw_query(d, ci, pos, end, n=None, gene=None, mark=None):
+    n = len(ci) if n is None else n
+    gene = np.zeros(max(1, n), np.uint32) if gene is None else gene
+    mark = np.zeros(max(1, n), np.int32) if mark is None else mark
+    assert d.L.dropest_annotation_query(d.h, n, ci.ctypes.data, pos.ctypes.data, end.ctypes.data, gene.ctypes.data, mark.ctypes.data) == 0, d.L.dropest_annotation_last_error()
+    return gene[:n], mark[:n]
+
+
+def _arrays(d, queries):
+    ci = np.array([d.chr_index.get(c, -1) for c, _, _ in queries], np.int32)
+    return ci, np.array([p for _, p, _ in queries], np.uint32), np.array([e for _, _, e in queries], np.uint32)
+
+
+@pytest.mark.parametrize("stream", ac.STREAMS)
+def test_device_annotation_on_generated_files(cases, stream):
+    """One call over the whole query list; query by query the oracle's answer, and the model's on simple files.  The kernel may
+    leave a query to the host (mark -2) only where more than 16 transcripts cover one of its two end points."""
+    case = cases[stream]
+    m = case.model
+    o, d = ob.GeneAnnotationOracle(case.path), DeviceAnnotation(Product(case.path))
+    got = d.query([c for c, _, _ in case.queries], [p for _, p, _ in case.queries], [e for _, _, e in case.queries])
+    n_left = 0
+    for (chr_, pos, end), g in zip(case.queries, got):
+        want = o.gene_for_read(chr_, pos, end)
+        depths = m.depths_of_read(chr_, pos, end)
+        where = (chr_, pos, end, "got", g, "oracle", want, "depth", depths, m.class_of_read(chr_, pos, end) if case.simple else "-")
+        if g is not None and g[1] == -2:
+            assert case.simple and max(depths) > CAP, where
+            n_left += 1
+            continue
+        assert g == want, where
+        if case.simple:
+            assert g == m.gene_for_read(chr_, pos, end), where
+            # include/dropest_annotation.h: more than 16 transcripts at an end point are always left to the host -- never answered from the first 16
+            assert g is None or max(depths) <= CAP, where
+    if stream.startswith("dense"):
+        n_deep = sum(1 for q in case.queries if max(m.depths_of_read(*q)) > CAP)
+        print(stream, "queries", len(case.queries), "left to the host", n_left, "with more than 16 transcripts at an end point", n_deep)
+        assert n_left >= 1
+    else:
+        assert n_left == 0
+    d.close()
+
+
+@pytest.mark.parametrize("stream", ac.STREAMS)
+def test_device_annotation_launch_edges(cases, stream):
+    case = cases[stream]
+    d = DeviceAnnotation(Product(case.path))
+    ci, pos, end = _arrays(d, case.queries)
+    assert len(ci) > 4097
+    gene, mark = _raw_query(d, ci, pos, end)
+    for n in (1, 255, 256, 257, 4097):
+        # the same queries cut to n, from the front and from a place in the middle (another block, another lane)
+        for at in (0, 1000):
+            g = np.full(n + 1, 0xABCD1234, np.uint32); mk = np.full(n + 1, -77, np.int32)
+            g_n, m_n = _raw_query(d, ci[at:at + n].copy(), pos[at:at + n].copy(), end[at:at + n].copy(), n=n, gene=g, mark=mk)
+            assert np.array_equal(m_n, mark[at:at + n]) and np.array_equal(g_n, gene[at:at + n]), (n, at)
+            assert g[n] == 0xABCD1234 and mk[n] == -77                      # nothing behind the n-th answer is written
+    n_chr = len(d.chr_index)
+    for bad in (-1, n_chr, n_chr + 5, -2 ** 31, 2 ** 31 - 1):
+        g_b, m_b = _raw_query(d, np.full(300, bad, np.int32), pos[:300].copy(), end[:300].copy())
+        assert (m_b == -1).all() and (g_b == 0xFFFFFFFF).all(), bad
+    g = np.full(4, 0xABCD1234, np.uint32); mk = np.full(4, -77, np.int32)
+    _raw_query(d, ci[:4].copy(), pos[:4].copy(), end[:4].copy(), n=0, gene=g, mark=mk)
+    assert (g == 0xABCD1234).all() and (mk == -77).all()
+    d.close()
+
+
+def _stream_child(path, npz):
+    """In a process of its own: torch brings the HIP runtime up first and the library binds to the same one (the order bench.py keeps), so that
+    a stream of torch's is a stream the library can launch on."""
+    import torch
+    torch.cuda.init()
+    q = np.load(npz)
+    d = DeviceAnnotation(Product(path))
+    ci = np.array([d.chr_index.get(c, -1) for c in q["chr"]], np.int32)
+    pos, end = np.ascontiguousarray(q["pos"], np.uint32), np.ascontiguousarray(q["end"], np.uint32)
+    gene, mark = _raw_query(d, ci, pos, end)
+    d.L.dropest_annotation_query_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64] + [C.c_void_p] * 5
+    n = len(ci)
+    s = torch.cuda.Stream()
+    assert s.cuda_stream != 0
+    with torch.cuda.stream(s):
+        t_ci = torch.from_numpy(ci).cuda()
+        t_pos, t_end = torch.from_numpy(pos.view(np.int32)).cuda(), torch.from_numpy(end.view(np.int32)).cuda()
+        t_gene, t_mark = torch.full((n + 64,), 0x5A5A5A5A, dtype=torch.int32, device="cuda"), torch.full((n + 64,), -77, dtype=torch.int32, device="cuda")
+        assert d.L.dropest_annotation_query_device(d.h, C.c_void_p(s.cuda_stream), n, t_ci.data_ptr(), t_pos.data_ptr(), t_end.data_ptr(), t_gene.data_ptr(), t_mark.data_ptr()) == 0
+        # n == 0 launches nothing
+        assert d.L.dropest_annotation_query_device(d.h, C.c_void_p(s.cuda_stream), 0, None, None, None, None, None) == 0
+    s.synchronize()
+    g_d, m_d = t_gene.cpu().numpy(), t_mark.cpu().numpy()
+    assert np.array_equal(g_d[:n].view(np.uint32), gene) and np.array_equal(m_d[:n], mark)
+    assert (g_d[n:] == 0x5A5A5A5A).all() and (m_d[n:] == -77).all()
+    assert (mark == -2).any() == ("dense" in os.path.basename(path))
+    d.close()
+    print("STREAM_OK %d" % n)
+
+
+@pytest.mark.parametrize("stream", ac.STREAMS)
+def test_device_annotation_of_device_arrays_on_a_stream(cases, stream, tmp_path):
+    """dropest_annotation_query_device on a stream of torch's, arrays as torch tensors == dropest_annotation_query"""
+    import subprocess
+    import sys
+    case = cases[stream]
+    npz = str(tmp_path / "queries.npz")
+    np.savez(npz, chr=np.array([c for c, _, _ in case.queries]), pos=np.array([p for _, p, _ in case.queries], np.uint32),
+             end=np.array([e for _, _, e in case.queries], np.uint32))
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    res = subprocess.run([sys.executable, os.path.abspath(__file__), case.path, npz], capture_output=True, text=True, timeout=300,
+                         env=dict(os.environ, PYTHONPATH=root + os.pathsep + os.environ.get("PYTHONPATH", "")))
+    assert res.returncode == 0 and "STREAM_OK %d" % len(case.queries) in res.stdout, res.stdout + res.stderr
+
+
+if __name__ == "__main__":
+    import sys
+    _stream_child(sys.argv[1], sys.argv[2])

@@ -59,6 +59,7 @@ def _run(tmp_path, mode, bams, min_before, min_after, wl="-", threads=3, env=Non
     rep = re.findall(r"\((\d+) guesses repaired\)", res.stderr)
     stats = json.loads(res.stdout.strip().splitlines()[-1])
     stats["_guesses_repaired"] = sum(int(x) for x in rep)
+    stats["_records_to_host"] = sum(int(x) for x in re.findall(r"(\d+) records with something new", res.stderr))   # n_needs of the device path's trace line
     d = rr.read_rds(out + ".rds")
     cm, genes, cells = rr.dgcmatrix_to_dense(d["cm"])
     got = {(genes[r], cells[c]): int(cm[r, c]) for r, c in zip(*np.nonzero(cm))}
@@ -333,6 +334,68 @@ def test_genes_from_a_gtf_annotation(tmp_path):
     assert cells_d == cells and got_d == got
     assert {k: stats_d[k] for k in ("total_reads", "cant_parse", "low_quality", "saved")} == {k: stats[k] for k in ("total_reads", "cant_parse", "low_quality", "saved")}
     assert sum(1 for k in kept if k[4] & 1) > 100 and sum(1 for k in kept if k[2] is None) > 1000    # half-annotated and intergenic reads
+
+
+def test_genes_at_deep_loci_are_decided_by_the_host(tmp_path):
+    """-g on the device BAM path where the annotation kernel gives up: alignments whose end points come from the dense annotation's query
+    list (annotation_cases.py), so that every branch of get_gene_from_reference occurs and, at loci of more than 16 transcripts, the kernel
+    answers -2 and bam_resolve_annotated_kernel hands the record to the host (gene cleared, UMI overwritten with 1).  The host must parse and
+    annotate those records itself and put their own UMI back: matrices, cells and counters are the oracle's, through the host reader and
+    through the device path, and the device path's count of records handed to the host covers the reads the model puts at such loci."""
+    import annotation_cases as ac
+    import annotation_model as am
+    from oracle import binding as ob
+    case = ac.make(tmp_path, "dense")
+    ann, model = ob.GeneAnnotationOracle(case.path), case.model
+    refs = [(c, 1_000_000) for c in case.chromosomes] + [("chrUn", 1000)]
+    usable = [(c, p, e) for c, p, e in case.queries if c in case.chromosomes and e > p and e < 1_000_000]
+    s = SynthStream(n_reads=len(usable), n_cells=15, n_genes=10, umi_len=8)
+    cb, umi, _, _ = s.generate_host()
+    rng = np.random.default_rng(16)
+    recs, kept, n_unknown, n_deep, n_deep_one, n_deep_many, classes = [], [], 0, 0, 0, 0, set()
+    for i, (chr_, p, end) in enumerate(usable):
+        c, u = capi.unpack_code(cb[i]), capi.unpack_code(umi[i])
+        rid = len(refs) - 1 if i % 50 == 0 else case.chromosomes.index(chr_)
+        ln = end - p
+        kind = int(rng.integers(0, 4))
+        if kind == 0 and ln >= 3:                                                   # spliced: the end point lies behind an N
+            a, b = int(rng.integers(1, min(30, ln - 1))), 1
+            cigar = [(a, "M"), (ln - a - b, "N"), (b, "M")]
+        elif kind == 1 and ln >= 4:
+            cigar = [(4, "S"), (ln - 3, "M"), (2, "I"), (2, "D"), (1, "M")]
+        elif kind == 2:
+            cigar = [(ln, "M"), (6, "S")]
+        else:
+            cigar = [(ln, "M")]
+        assert p + sum(n for n, op in cigar if op in "MDN=X") == end
+        seq = ("ACGT" * (1 + sum(n for n, op in cigar if op in "MIS=X") // 4))[:sum(n for n, op in cigar if op in "MIS=X")]
+        recs.append(bw.record(rid, p, "r%d" % i, seq=seq, tags=[("CB", "Z", c), ("UB", "Z", u)], cigar=cigar))
+        got = ann.gene_for_read(refs[rid][0], p, end)
+        if got is None:
+            n_unknown += 1
+            continue
+        kept.append((c, u, got[0] or None, refs[rid][0], got[1]))
+        assert got == model.gene_for_read(chr_, p, end)
+        sets, depths = model.sets_of_read(chr_, p, end), model.depths_of_read(chr_, p, end)
+        classes.add(am.classify(*sets))
+        over = [len(x) for x, d in zip(sets, depths) if d > 16]
+        n_deep += bool(over); n_deep_one += any(n == 1 for n in over); n_deep_many += any(n > 16 for n in over)
+    assert classes == set(am.CLASSES) and n_deep_one > 50 and n_deep_many > 50
+    bam = str(tmp_path / "deep.bam")
+    bw.write_bam(bam, refs, recs, block=30_000)
+    os.environ["DROPEST_GTF"] = case.path
+    try:
+        got, cells, stats, d = _run(tmp_path, "filled", [bam], 2, 3)
+        got_d, cells_d, stats_d, _ = _run(tmp_path / "device", "filled", [bam], 2, 3, env={"DROPEST_BAM_DEVICE": "1", "DROPEST_BAM_DEVICE_WINDOW_MB": "1", "DROPEST_BAM_TRACE": "1"})
+    finally:
+        del os.environ["DROPEST_GTF"]
+    want, cols = _oracle(kept, 2, 3)
+    print("accepted records", len(kept), "with more than 16 transcripts at an end point", n_deep, "handed to the host by the device path", stats_d["_records_to_host"])
+    assert cells == cols and got == want and len(want) > 100
+    assert stats["cant_parse"] == n_unknown > 0 and stats["saved"] == len(kept)
+    assert cells_d == cols and got_d == want
+    assert {k: stats_d[k] for k in ("total_reads", "cant_parse", "low_quality", "saved")} == {k: stats[k] for k in ("total_reads", "cant_parse", "low_quality", "saved")}
+    assert stats_d["_records_to_host"] >= n_deep > 0                                 # the host route ran
 
 
 def test_umi_quality_tags_reach_reads_per_umi_per_cell(tmp_path):
