@@ -7,7 +7,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIB_DIR, "libdropest_amd.so")
-SOURCES = ["dropest_amd.hip", "synth_api.hip", "annotation_api.hip", "bgzf_api.hip"]
+SOURCES = ["dropest_amd.hip", "synth_api.hip", "annotation_api.hip", "bgzf_api.hip", "deflate_api.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function", "-pthread"]
 OBJ_DIR = os.path.join(LIB_DIR, "obj")
 
@@ -72,6 +72,7 @@ FACADE_LIB = os.path.join(LIB_DIR, "libdropest_facade.so")
 FACADE_TEST = os.path.join(HERE, "..", "tests", "cpp", "test_facade")
 BAM_TOOL = os.path.join(HERE, "..", "tests", "cpp", "bam_to_counts")
 RATE_TOOL = os.path.join(HERE, "..", "tests", "cpp", "add_record_rate")
+RDS_TOOL = os.path.join(HERE, "..", "tests", "cpp", "bam_to_rds")
 
 
 def build_facade(force=False, verbose=False):
@@ -85,11 +86,12 @@ def build_facade(force=False, verbose=False):
     test_src = os.path.join(HERE, "..", "tests", "cpp", "test_facade.cpp")
     bam_tool_src = os.path.join(HERE, "..", "tests", "cpp", "bam_to_counts.cpp")
     rate_src = os.path.join(HERE, "..", "tests", "cpp", "add_record_rate.cpp")
+    rds_tool_src = os.path.join(HERE, "..", "tests", "cpp", "bam_to_rds.cpp")
     newest = max(os.path.getmtime(x) for x in (src, rds, bam, ga, os.path.join(CSRC, "host", "rds_writer.h"), os.path.join(CSRC, "host", "bam_ingest.h"),
                                                os.path.join(CSRC, "host", "gene_annotation.h"),
-                                               hdr, test_src, bam_tool_src, rate_src, LIB))
-    if not force and os.path.exists(FACADE_LIB) and os.path.exists(FACADE_TEST) and os.path.exists(BAM_TOOL) and os.path.exists(RATE_TOOL) and \
-            min(os.path.getmtime(FACADE_LIB), os.path.getmtime(FACADE_TEST), os.path.getmtime(BAM_TOOL), os.path.getmtime(RATE_TOOL)) > newest:
+                                               hdr, test_src, bam_tool_src, rate_src, rds_tool_src, LIB))
+    if not force and os.path.exists(FACADE_LIB) and os.path.exists(FACADE_TEST) and os.path.exists(BAM_TOOL) and os.path.exists(RATE_TOOL) and os.path.exists(RDS_TOOL) and \
+            min(os.path.getmtime(FACADE_LIB), os.path.getmtime(FACADE_TEST), os.path.getmtime(BAM_TOOL), os.path.getmtime(RATE_TOOL), os.path.getmtime(RDS_TOOL)) > newest:
         return FACADE_LIB, FACADE_TEST
     cmds = [
         ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", src, rds, bam, ga, "-o", FACADE_LIB, "-L" + LIB_DIR, "-ldropest_amd", "-lz",
@@ -99,6 +101,8 @@ def build_facade(force=False, verbose=False):
         ["g++", "-O2", "-std=c++17", "-Wall", bam_tool_src, "-o", BAM_TOOL, "-L" + LIB_DIR, "-ldropest_facade", "-ldropest_amd",
          "-Wl,-rpath,$ORIGIN/../../dropest_amd/lib"],
         ["g++", "-O2", "-std=c++17", "-Wall", rate_src, "-o", RATE_TOOL, "-L" + LIB_DIR, "-ldropest_facade", "-ldropest_amd",
+         "-Wl,-rpath,$ORIGIN/../../dropest_amd/lib"],
+        ["g++", "-O2", "-std=c++17", "-Wall", rds_tool_src, "-o", RDS_TOOL, "-L" + LIB_DIR, "-ldropest_facade", "-ldropest_amd",
          "-Wl,-rpath,$ORIGIN/../../dropest_amd/lib"],
     ]
     for cmd in cmds:

@@ -1,6 +1,7 @@
 // facade.cpp -- see facade.h.  Host-side packing and result relaying only; no counting happens here.
 #include "facade.h"
 #include "rds_writer.h"
+#include "../../../include/dropest_deflate.h"
 
 #include <algorithm>
 #include <atomic>
@@ -1322,6 +1323,50 @@ Rds::ValuePtr ResultsPrinter::results_list(const CellsDataContainer &c) const {
 	return named_list(std::move(d));
 }
 
+// Rds::Compressor over include/dropest_deflate.h: the pieces of a batch side by side in the handle's pinned buffer, one launch, the stream back
+// as the batch's first entry.  Any device error: this batch (and, when the handle could not be made, every batch) through zlib on the host.
+struct DeviceCompressor : Rds::Compressor {
+	dropest_deflate_batch *handle = nullptr;
+	Rds::HostCompressor host;
+	std::string error;
+	size_t device_batches = 0, host_batches = 0;
+	DeviceCompressor(int device, size_t batch) : batch(batch) {
+		// (a piece may overshoot its 2 MB by one element and a batch by one piece: room for both)
+		if (dropest_deflate_batch_create(device, batch + (size_t(4) << 20), &handle)) { error = dropest_deflate_last_error(); handle = nullptr; }
+	}
+	~DeviceCompressor() override { dropest_deflate_batch_destroy(handle); }
+	size_t batch_bytes() const override { return batch; }
+	void compress(const std::vector<std::vector<unsigned char>> &pieces, std::vector<std::vector<unsigned char>> &out) override {
+		size_t total = 0;
+		std::vector<size_t> at(pieces.size());
+		for (size_t k = 0; k < pieces.size(); ++k) { at[k] = total; total += pieces[k].size(); }
+		uint8_t *in = nullptr;
+		const uint8_t *stream = nullptr;
+		uint64_t n = 0;
+		bool ok = handle && total <= batch + (size_t(4) << 20) && dropest_deflate_batch_input(handle, &in) == 0;
+		if (ok) {
+			Rds::parallel_pieces(pieces.size(), 0, [&](size_t k) { std::memcpy(in + at[k], pieces[k].data(), pieces[k].size()); });
+			ok = dropest_deflate_batch_run(handle, total, &stream, &n, nullptr) == 0;
+			if (!ok) error = dropest_deflate_last_error();
+		}
+		if (!ok) { ++host_batches; if (error.empty()) error = "a batch larger than the device buffers"; host.compress(pieces, out); return; }
+		++device_batches;
+		out.assign(pieces.size(), {});
+		if (!out.empty()) out[0].assign(stream, stream + n);
+	}
+private:
+	size_t batch;
+};
+
+void ResultsPrinter::save_rds(const Rds::ValuePtr &v, const std::string &path) const {
+	compression_error.clear();
+	if (!device_compression) { Rds::save(v, path); return; }
+	DeviceCompressor dc(compression_device, DEVICE_BATCH_BYTES);
+	Rds::save(v, path, dc);
+	compression_error = dc.error;
+	if (getenv("DROPEST_RDS_TRACE")) std::fprintf(stderr, "[rds] batches: %zu on the device, %zu on the host%s%s\n", dc.device_batches, dc.host_batches, dc.error.empty() ? "" : ": ", dc.error.c_str());
+}
+
 void ResultsPrinter::save_intron_exon_matrices(const CellsDataContainer &c, const std::string &filename) const {   // ResultsPrinter.cpp:455-474
 	using namespace Rds;
 	auto m = [&](const char *code) {
@@ -1331,7 +1376,7 @@ void ResultsPrinter::save_intron_exon_matrices(const CellsDataContainer &c, cons
 	std::string base = filename;
 	const size_t dot = filename.find_last_of('.');
 	if (dot != std::string::npos && filename.substr(dot + 1) == "rds") base = filename.substr(0, dot);
-	Rds::save(named_list({{"exon", m("e")}, {"intron", m("i")}, {"spanning", m("BA")}}), base + ".matrices.rds");
+	save_rds(named_list({{"exon", m("e")}, {"intron", m("i")}, {"spanning", m("BA")}}), base + ".matrices.rds");
 }
 
 void ResultsPrinter::save_results(const CellsDataContainer &c, const std::string &filename) const {   // ResultsPrinter.cpp:23-79
@@ -1340,9 +1385,35 @@ void ResultsPrinter::save_results(const CellsDataContainer &c, const std::string
 	if (dot != std::string::npos && filename.substr(dot + 1) == "rds") base = filename.substr(0, dot);
 	const Rds::ValuePtr v = results_list(c);
 	const auto t_save = std::chrono::steady_clock::now();
-	Rds::save(v, base + ".rds");                                        // save_rds (:442-452)
+	save_rds(v, base + ".rds");                                        // save_rds (:442-452)
 	if (getenv("DROPEST_RDS_TRACE")) std::fprintf(stderr, "[rds] serialise + deflate + write %.1f ms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_save).count());
 	if (write_matrix) save_mtx(c, base);
 }
 
 }  // namespace Estimation
+
+// test hook (tests/test_gpu_rds_device.py): one value of matrix-like vectors (n row indices, n small counts as doubles, n / 8 strings) saved by
+// the host writer and through the facade's device compressor in batches of `batch_bytes`; 0 = both written, *device_error = a device error
+extern "C" int dropest_test_rds_device_save(const char *host_path, const char *device_path, uint64_t n, int device, uint64_t batch_bytes,
+                                            uint64_t *device_batches, uint64_t *host_batches, char *device_error, uint64_t device_error_cap) {
+	try {
+		auto value = [&] {
+			std::vector<uint32_t> rows(n), counts(n);
+			uint64_t x = 88172645463325252ull;
+			for (uint64_t k = 0; k < n; ++k) { x ^= x << 13; x ^= x >> 7; x ^= x << 17; rows[k] = uint32_t(k % 30011u); counts[k] = 1u + uint32_t(__builtin_ctzll(x | (1ull << 20))); }
+			std::vector<std::string> names(n / 8);
+			for (size_t k = 0; k < names.size(); ++k) names[k] = "CELL" + std::to_string(k * 7919u % 100003u);
+			return Rds::named_list({{"i", Rds::integers_from_u32(std::move(rows))}, {"x", Rds::reals_from_u32(std::move(counts))}, {"names", Rds::strings(std::move(names))}});
+		};
+		Rds::save(value(), host_path);
+		Estimation::DeviceCompressor dc(device, size_t(batch_bytes));
+		Rds::save(value(), device_path, dc);
+		if (device_batches) *device_batches = dc.device_batches;
+		if (host_batches) *host_batches = dc.host_batches;
+		if (device_error && device_error_cap) std::snprintf(device_error, device_error_cap, "%s", dc.error.c_str());
+		return 0;
+	} catch (const std::exception &e) {
+		if (device_error && device_error_cap) std::snprintf(device_error, device_error_cap, "%s", e.what());
+		return 1;
+	}
+}

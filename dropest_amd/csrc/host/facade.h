@@ -543,6 +543,20 @@ public:
 	// aligned_reads_per_cell, aligned_umis_per_cell, requested_umis_per_cb, requested_reads_per_cb[, reads_per_umi_per_cell]),
 	// written natively in R's serialisation format (rds_writer.h); + the matrix triple with write_matrix
 	void save_results(const CellsDataContainer &container, const std::string &filename) const;
+	// The .rds files' DEFLATE on the device (include/dropest_deflate.h) instead of zlib level 4 on host threads: host threads materialise a
+	// batch of pieces, the batch goes up through pinned memory, one launch turns it into BGZF blocks (gzip members of <= 65 280 bytes), they
+	// come back and are written in order while the next batch materialises.  In flight: two batches of DEVICE_BATCH_BYTES of serialised bytes on
+	// the host, one in pinned memory, about 7 x DEVICE_BATCH_BYTES of device memory.  Off by default.  A batch the device fails on goes
+	// through the host compressor, the file is written all the same, and device_compression_error() says what happened ("" = nothing).
+	static constexpr size_t DEVICE_BATCH_BYTES = size_t(32) << 20;
+	void set_device_compression(bool on, int device = 0) { device_compression = on; compression_device = device; }
+	const std::string &device_compression_error() const { return compression_error; }
+private:
+	bool device_compression = false;
+	int compression_device = 0;
+	mutable std::string compression_error;
+	void save_rds(const std::shared_ptr<Rds::Value> &v, const std::string &path) const;
+public:
 	std::shared_ptr<Rds::Value> results_list(const CellsDataContainer &container) const;
 };
 

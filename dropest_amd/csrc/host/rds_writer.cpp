@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <cstring>
 #include <exception>
+#include <future>
 #include <mutex>
 #include <stdexcept>
 #include <thread>
@@ -219,20 +220,6 @@ public:
 	}
 };
 
-// one gzip member (RFC 1952) around `in`
-void gzip_member(const std::vector<unsigned char> &in, std::vector<unsigned char> &out, int level) {
-	z_stream z{};
-	if (deflateInit2(&z, level, Z_DEFLATED, 15 + 16, 8, Z_DEFAULT_STRATEGY) != Z_OK) throw std::runtime_error("rds: deflateInit2 failed");
-	out.resize(deflateBound(&z, uLong(in.size())) + 32);
-	z.next_in = const_cast<Bytef *>(in.data()); z.avail_in = uInt(in.size());
-	z.next_out = out.data(); z.avail_out = uInt(out.size());
-	const int rc = deflate(&z, Z_FINISH);
-	const size_t n = z.total_out;
-	deflateEnd(&z);
-	if (rc != Z_STREAM_END) throw std::runtime_error("rds: deflate failed");
-	out.resize(n);
-}
-
 ValuePtr make(Value::Kind k) { auto p = std::make_shared<Value>(); p->kind = k; return p; }
 
 }  // namespace
@@ -287,6 +274,59 @@ ValuePtr dgCMatrix(std::vector<uint32_t> colptr, std::vector<uint32_t> rowidx, s
 	return m;
 }
 
+void gzip_member(const unsigned char *in, size_t n_in, std::vector<unsigned char> &out, int level) {
+	z_stream z{};
+	if (deflateInit2(&z, level, Z_DEFLATED, 15 + 16, 8, Z_DEFAULT_STRATEGY) != Z_OK) throw std::runtime_error("rds: deflateInit2 failed");
+	const size_t at = out.size();
+	out.resize(at + deflateBound(&z, uLong(n_in)) + 32);
+	z.next_in = const_cast<Bytef *>(in); z.avail_in = uInt(n_in);
+	z.next_out = out.data() + at; z.avail_out = uInt(out.size() - at);
+	const int rc = deflate(&z, Z_FINISH);
+	const size_t n = z.total_out;
+	deflateEnd(&z);
+	if (rc != Z_STREAM_END) throw std::runtime_error("rds: deflate failed");
+	out.resize(at + n);
+}
+
+void HostCompressor::compress(const std::vector<std::vector<unsigned char>> &pieces, std::vector<std::vector<unsigned char>> &out) {
+	out.assign(pieces.size(), {});
+	parallel_pieces(pieces.size(), threads, [&](size_t k) { gzip_member(pieces[k].data(), pieces[k].size(), out[k], 4); });
+}
+
+void save(const ValuePtr &value, const std::string &path, Compressor &compressor, unsigned threads) {
+	Plan plan;
+	plan.header();
+	plan.item(*value);
+	const size_t n = plan.pieces();
+	FILE *f = std::fopen(path.c_str(), "wb");
+	if (!f) throw std::runtime_error("Can't open file: " + path);
+	bool ok = true;
+	using Batch = std::vector<std::vector<unsigned char>>;
+	std::future<Batch> pending;                     // the batch before this one, being compressed
+	auto drain = [&] {
+		if (!pending.valid()) return;
+		const Batch done = pending.get();
+		for (auto const &m : done) ok = ok && (m.empty() || std::fwrite(m.data(), 1, m.size(), f) == m.size());
+	};
+	try {
+		const size_t per_batch = std::max<size_t>(1, compressor.batch_bytes() / PIECE_BYTES);
+		for (size_t first = 0; first < n; first += per_batch) {
+			const size_t count = std::min(per_batch, n - first);
+			auto raw = std::make_shared<Batch>(count);
+			parallel_pieces(count, threads, [&](size_t k) { plan.materialise(first + k, (*raw)[k]); });
+			drain();
+			pending = std::async(std::launch::async, [raw, &compressor] { Batch out; compressor.compress(*raw, out); if (out.size() != raw->size()) throw std::runtime_error("rds: the compressor lost a piece"); return out; });
+		}
+		drain();
+	} catch (...) {
+		if (pending.valid()) pending.wait();
+		std::fclose(f);
+		throw;
+	}
+	ok = (std::fclose(f) == 0) && ok;
+	if (!ok) throw std::runtime_error("rds: write failed");
+}
+
 void save(const ValuePtr &value, const std::string &path, unsigned threads) {
 	Plan plan;
 	plan.header();
@@ -296,7 +336,7 @@ void save(const ValuePtr &value, const std::string &path, unsigned threads) {
 	parallel_pieces(n, threads, [&](size_t k) {
 		std::vector<unsigned char> bytes;
 		plan.materialise(k, bytes);
-		gzip_member(bytes, member[k], 4);        // (level 4, as the single stream of earlier rounds: "wb4")
+		gzip_member(bytes.data(), bytes.size(), member[k], 4);        // (level 4, as the single stream of earlier rounds: "wb4")
 	});
 	FILE *f = std::fopen(path.c_str(), "wb");
 	if (!f) throw std::runtime_error("Can't open file: " + path);

@@ -65,6 +65,27 @@ ValuePtr reals_from_u32(std::vector<uint32_t> v);
 // threads: host threads that swap + deflate the pieces (0: up to 16 of the machine's; 1: everything on the calling thread).
 void save(const ValuePtr &value, const std::string &path, unsigned threads = 0);
 
+// What deflates the pieces (round 7).  save() materialises the pieces of a BATCH on host threads, hands the batch over, and writes what comes
+// back in order while the next batch materialises.  out gets one entry per piece; one after the other they must be whole gzip members (RFC 1952)
+// that inflate to the pieces one after the other (a compressor that deflates the batch as one range hands everything back in out[0]).
+// In flight at any time: at most TWO batches -- 2 x batch_bytes() of serialised bytes (+ one piece of ~2 MB each, where a batch closes) and their
+// compressed bytes; the file as a whole is never held.  compress() runs on one thread at a time.
+struct Compressor {
+	virtual ~Compressor() = default;
+	virtual void compress(const std::vector<std::vector<unsigned char>> &pieces, std::vector<std::vector<unsigned char>> &out) = 0;
+	virtual size_t batch_bytes() const { return size_t(32) << 20; }
+};
+// the default: one zlib level-4 member per piece on up to `threads` host threads -- the bytes save(value, path, threads) writes
+struct HostCompressor : Compressor {
+	explicit HostCompressor(unsigned threads_ = 0) : threads(threads_) {}
+	void compress(const std::vector<std::vector<unsigned char>> &pieces, std::vector<std::vector<unsigned char>> &out) override;
+	unsigned threads;
+};
+// one gzip member around in[0 .. n), APPENDED to out
+void gzip_member(const unsigned char *in, size_t n, std::vector<unsigned char> &out, int level = 4);
+// save(value, path) through `compressor`; threads: host threads that materialise the pieces
+void save(const ValuePtr &value, const std::string &path, Compressor &compressor, unsigned threads = 0);
+
 // fn(piece) for piece = 0 .. n - 1 on up to `threads` host threads (0: up to 16 of the machine's); the first exception is rethrown
 void parallel_pieces(size_t n, unsigned threads, const std::function<void(size_t)> &fn);
 

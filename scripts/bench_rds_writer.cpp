@@ -1,18 +1,47 @@
 // Times Rds::save (dropest_amd/csrc/host/rds_writer.cpp) on a list shaped like a C2 result: two dgCMatrix of `nnz` entries in all (12 bytes each
 // in the serialisation), saturation_info's three vectors of `mol` entries (reads, cbs, umis), per-cell vectors.  Host-only.
 //   g++ -O2 -std=c++17 scripts/bench_rds_writer.cpp dropest_amd/csrc/host/rds_writer.cpp -o /tmp/bench_rds -lz -pthread && /tmp/bench_rds 38000000 4000000
+// With -DDROPEST_BENCH_DEVICE -Ldropest_amd/lib -ldropest_amd -Wl,-rpath,$PWD/dropest_amd/lib a fourth leg saves the same list through Rds::save's
+// compressor overload with the device compressor (include/dropest_deflate.h, batches of 32 MB as the facade's) -- same job, same box as the host legs.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <string>
 #include <vector>
 #include "../dropest_amd/csrc/host/rds_writer.h"
+#ifdef DROPEST_BENCH_DEVICE
+#include <cstring>
+#include "../include/dropest_deflate.h"
+namespace {
+struct DeviceCompressor : Rds::Compressor {
+	dropest_deflate_batch *h = nullptr;
+	static constexpr size_t BATCH = size_t(32) << 20;
+	DeviceCompressor() { if (dropest_deflate_batch_create(0, BATCH + (size_t(4) << 20), &h)) { fprintf(stderr, "%s\n", dropest_deflate_last_error()); exit(1); } }
+	~DeviceCompressor() override { dropest_deflate_batch_destroy(h); }
+	size_t batch_bytes() const override { return BATCH; }
+	void compress(const std::vector<std::vector<unsigned char>> &pieces, std::vector<std::vector<unsigned char>> &out) override {
+		uint8_t *in = nullptr; const uint8_t *stream = nullptr; uint64_t n = 0;
+		std::vector<size_t> at(pieces.size()); size_t total = 0;
+		for (size_t k = 0; k < pieces.size(); ++k) { at[k] = total; total += pieces[k].size(); }
+		dropest_deflate_batch_input(h, &in);
+		Rds::parallel_pieces(pieces.size(), 0, [&](size_t k) { std::memcpy(in + at[k], pieces[k].data(), pieces[k].size()); });
+		if (dropest_deflate_batch_run(h, total, &stream, &n, nullptr)) { fprintf(stderr, "%s\n", dropest_deflate_last_error()); exit(1); }
+		out.assign(pieces.size(), {}); out[0].assign(stream, stream + n);
+	}
+};
+}
+#endif
 
 int main(int argc, char **argv) {
 	using namespace Rds;
 	const size_t nnz = argc > 1 ? size_t(atof(argv[1])) : 38000000, mol = argc > 2 ? size_t(atof(argv[2])) : 4000000, cols = 5000, genes = 30000;
 	const std::string out = argc > 3 ? argv[3] : "/tmp/bench_rds.rds";
-	for (unsigned threads : {1u, 4u, 16u}) {
+#ifdef DROPEST_BENCH_DEVICE
+	const unsigned legs[] = {16u, 0u, 16u, 0u};      // 0 = the device compressor; alternating with the host writer on 16 threads
+#else
+	const unsigned legs[] = {1u, 4u, 16u};
+#endif
+	for (unsigned threads : legs) {
 		auto matrix = [&](size_t n) {
 			std::vector<uint32_t> p(cols + 1), i(n), x(n);
 			for (size_t c = 0; c <= cols; ++c) p[c] = uint32_t(c * n / cols);
@@ -29,6 +58,9 @@ int main(int argc, char **argv) {
 		auto v = named_list({{"cm", matrix(nnz / 2)}, {"cm_raw", matrix(nnz - nnz / 2)},
 		                     {"saturation_info", named_list({{"reads", integers(std::move(reads))}, {"cbs", strings(std::move(cbs))}, {"umis", strings(std::move(umis))}})}});
 		const auto t0 = std::chrono::steady_clock::now();
+#ifdef DROPEST_BENCH_DEVICE
+		if (!threads) { static DeviceCompressor dc; save(v, out, dc, 16); } else
+#endif
 		save(v, out, threads);
 		const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 		FILE *f = fopen(out.c_str(), "rb"); fseek(f, 0, SEEK_END); const long bytes = ftell(f); fclose(f);
