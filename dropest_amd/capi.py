@@ -195,6 +195,8 @@ def lib():
         "dropest_shard_set_reads_device": (C.c_int, [vp, vp, vp, vp, vp, C.c_uint64, C.c_uint64]),
         "dropest_shard_step": (C.c_int, [vp]),
         "dropest_shard_push_reads": (C.c_int, [vp, vp, vp, vp, vp, C.c_uint64, C.c_uint64]),
+        "dropest_shard_push_reads_device": (C.c_int, [vp, vp, vp, vp, vp, C.c_uint64, C.c_uint64, C.c_int32, vp]),
+        "dropest_deal_range": (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_int32, vp, P(C.c_uint32)]),
         "dropest_reserve_reads": (C.c_int, [vp, C.c_uint64]),
         "dropest_shard_group_step": (C.c_int, [vp, C.c_int32]),
         "dropest_shard_matrix": (C.c_int, [vp, C.c_int, u64p, u64p, P(vp), P(vp), P(vp), P(vp)]),
@@ -236,7 +238,7 @@ EXPORTED_SYMBOLS = [
     "dropest_dev_copy_to_host", "dropest_dev_copy_from_host", "dropest_dev_count", "dropest_dev_sync",
     "dropest_rand_sequence", "dropest_table_sizes",
     "dropest_shard_unique_id", "dropest_shard_create", "dropest_shard_group_create", "dropest_shard_destroy", "dropest_shard_ctx",
-    "dropest_shard_set_reads_device", "dropest_shard_push_reads", "dropest_reserve_reads", "dropest_shard_step", "dropest_shard_group_step", "dropest_shard_matrix", "dropest_shard_matrix_form",
+    "dropest_shard_set_reads_device", "dropest_shard_push_reads", "dropest_shard_push_reads_device", "dropest_deal_range", "dropest_reserve_reads", "dropest_shard_step", "dropest_shard_group_step", "dropest_shard_matrix", "dropest_shard_matrix_form",
     "dropest_shard_merged_barcodes", "dropest_shard_phase_stats", "dropest_shard_set_option", "dropest_plan_columns",
     "dropest_key_width", "dropest_ctx_split", "dropest_shard_matrix_narrow", "dropest_shard_matrix_bytes", "dropest_add_umi_to_cell", "dropest_umi_first_seen", "dropest_resident_reads", "dropest_prefetch_raw_matrix_narrow", "dropest_narrow_matrix_possible", "dropest_count_matrix_csc_narrow",
     "dropest_prefetch_raw_matrix_bytes", "dropest_count_matrix_csc_bytes", "dropest_matrix_bytes_widen", "dropest_matrix_rider_widen", "dropest_set_raw_matrix_prefetch", "dropest_set_matrix_wire", "dropest_set_umi_dictionary", "dropest_debug_refresh", "dropest_push_reads_gather", "dropest_shard_set_umi_qualities", "dropest_shard_set_umi_qualities_var",
@@ -759,6 +761,17 @@ def plan_columns(barcode, first_global, n_genes, req_genes, req_umis, total_umis
     if rc != 0:
         raise DropestError(rc, lib().dropest_last_error().decode())
     return order[:k.value].copy()
+
+
+def deal_range(first_ordinal, n, quota, n_shards):
+    """[(shard, offset, count), ...]: the pieces a run of n reads starting at stream ordinal first_ordinal falls into when read k
+    belongs to shard min(n_shards - 1, k // quota) (dropest_deal_range; host logic, no GPU)."""
+    out = (C.c_uint64 * (3 * max(1, n_shards)))()
+    k = C.c_uint32()
+    rc = lib().dropest_deal_range(int(first_ordinal), int(n), int(quota), int(n_shards), out, C.byref(k))
+    if rc != 0:
+        raise DropestError(rc, lib().dropest_last_error().decode())
+    return [(int(out[3 * i]), int(out[3 * i + 1]), int(out[3 * i + 2])) for i in range(k.value)]
 
 
 def radix_plan(varying_mask):

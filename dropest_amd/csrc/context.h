@@ -166,6 +166,18 @@ struct ReadStore {
 		                              // last launch of a file unsubmitted for 23-28 ms: measured, dropped)
 		n += count;
 	}
+	// The same for arrays of ANOTHER device (dropest_shard_push_reads_device with a source that is not the store's GPU): peer copies on `on`, a stream
+	// of the store's device.  The caller has waited for whatever wrote the arrays on their own device; the store's device is current.
+	void push_peer(const uint64_t *d_cb, const uint64_t *d_umi, const uint32_t *d_gene, const uint32_t *d_aux, size_t count, int dst_device, int src_device, hipStream_t on) {
+		if (!count) return;
+		reserve(n + count);
+		HIP_CHECK(hipMemcpyPeerAsync(cb.p + n, dst_device, d_cb, src_device, count * 8, on));
+		HIP_CHECK(hipMemcpyPeerAsync(umi.p + n, dst_device, d_umi, src_device, count * 8, on));
+		HIP_CHECK(hipMemcpyPeerAsync(gene.p + n, dst_device, d_gene, src_device, count * 4, on));
+		HIP_CHECK(hipMemcpyPeerAsync(aux.p + n, dst_device, d_aux, src_device, count * 4, on));
+		HIP_CHECK(stream_wait(on));
+		n += count;
+	}
 	void wait() { if (copy) HIP_CHECK(stream_wait(copy)); }
 	void clear() { wait(); n = 0; }
 };

@@ -922,9 +922,13 @@ void BamController::parse_bam_files(const std::vector<std::string> &bam_files, C
 		// (a gene name, a chromosome, a string with N) are fetched as bytes and go through parse_one + the intern_* members in file order,
 		// exactly like the Needs of fast_window.  Windows grow from 1 MB of compressed bytes (the first ones meet most gene names).
 		// Every block's CRC-32 is checked on the device (the wave that inflated it reads it back).  Falls back to the host reader (returns false before anything was added) when
-		// the configuration needs what the kernels do not do: -r parameter files, gene = chromosome name, sharded containers.
+		// the configuration needs what the kernels do not do: -r parameter files, gene = chromosome name.
+		// A sharded container is fed the same way: ONE decoder, on the GPU of the shard the file's first read goes to and on that shard's stream, for the
+		// whole file (the record cut off at a window's end waits inside it); the container cuts every window at its quota boundaries and appends the
+		// pieces to the shards' resident reads, device to device.
 		auto device_file = [&]() -> bool {
-			if (_params_from_files || _gene_in_chromosome_name || !container.bulk_ingest_possible_at_all()) return false;
+			if (_params_from_files || _gene_in_chromosome_name || !container.bulk_ingest_possible_at_all(true)) return false;
+			const CellsDataContainer::IngestTarget target = container.next_read_target();
 			const auto t_enter = clk::now();
 			double ms_header = 0, ms_create = 0;
 			if (_tags.intronic_read_value.size() > 24 || _tags.intergenic_read_value.size() > 24) return false;
@@ -997,13 +1001,13 @@ void BamController::parse_bam_files(const std::vector<std::string> &bam_files, C
 			dropest_bam_decoder *dec = nullptr;
 			{
 				std::lock_guard<std::mutex> lk(decoder_cache_mutex());
-				auto it = decoder_cache().find(container.device());
+				auto it = decoder_cache().find(target.device);
 				if (it != decoder_cache().end()) { dec = it->second; decoder_cache().erase(it); }
 			}
 			if (dec && dropest_bam_decoder_reset(dec, &cfg)) { dropest_bam_decoder_destroy(dec); dec = nullptr; }
-			if (!dec && dropest_bam_decoder_create(container.device(), &cfg, &dec)) return false;       // (no GPU for this: the host reader does it)
-			// its kernels on the container's stream for this file: that one exists and has run kernels; one of the decoder's own is ~16 ms to make
-			if (container.handle() && dropest_bam_decoder_use_stream(dec, dropest_stream(container.handle()))) { dropest_bam_decoder_destroy(dec); return false; }
+			if (!dec && dropest_bam_decoder_create(target.device, &cfg, &dec)) return false;       // (no GPU for this: the host reader does it)
+			// its kernels on the container's stream (a sharded one: that shard's) for this file: that one exists and has run kernels; one of the decoder's own is ~16 ms to make
+			if (target.stream && dropest_bam_decoder_use_stream(dec, target.stream)) { dropest_bam_decoder_destroy(dec); return false; }
 			ms_create = since(t_enter) - ms_header;
 			struct Keep {    // back into the cache when the file went through, destroyed when it did not (whatever state an exception left)
 				dropest_bam_decoder *d; int device; bool ok = false;
@@ -1017,7 +1021,7 @@ void BamController::parse_bam_files(const std::vector<std::string> &bam_files, C
 					if (slot) dropest_bam_decoder_destroy(slot);
 					slot = d;
 				}
-			} keep_dec{dec, container.device()};
+			} keep_dec{dec, target.device};
 			// -g: the annotation's flat tables on the device (annotation_api.hip); the decoder asks it about the two ends of every alignment
 			struct FreeAnn { dropest_annotation *a = nullptr; ~FreeAnn() { if (a) dropest_annotation_destroy(a); } } ann;
 			Tools::GeneAnnotation::RefGenesContainer::Flat flat;
@@ -1031,7 +1035,7 @@ void BamController::parse_bam_files(const std::vector<std::string> &bam_files, C
 				fa.chr_seg_begin = flat.chr_seg_begin.data(); fa.seg_start = flat.seg_start.data(); fa.seg_end = flat.seg_end.data(); fa.seg_tr_begin = flat.seg_tr_begin.data();
 				fa.seg_tr = flat.seg_tr.data(); fa.tr_gene = flat.tr_gene.data(); fa.tr_exon_begin = flat.tr_exon_begin.data(); fa.tr_intron_begin = flat.tr_intron_begin.data();
 				fa.exon_start = flat.exon_start.data(); fa.exon_end = flat.exon_end.data(); fa.intron_start = flat.intron_start.data(); fa.intron_end = flat.intron_end.data();
-				if (dropest_annotation_create(container.device(), &fa, &ann.a)) return false;
+				if (dropest_annotation_create(target.device, &fa, &ann.a)) return false;
 				std::unordered_map<std::string, int32_t> chr_index;
 				for (size_t k = 0; k < flat.chr_names.size(); ++k) chr_index.emplace(flat.chr_names[k], int32_t(k));
 				std::vector<int32_t> ann_chr_of_ref(refs.size(), -1);
@@ -1426,8 +1430,8 @@ void BamController::parse_bam_files(const std::vector<std::string> &bam_files, C
 				// per accepted read beside the columns; anything else -> the window's records come back as bytes (below)
 				const bool has_q = w.any_gene && w.quality_len_max > 0;
 				const uint32_t q_len = w.quality_len_max;
-				const bool q_bulk = has_q && w.quality_len_min == w.quality_len_max && container.bulk_ingest_possible_with_quality(q_len);
-				if (has_q ? !q_bulk : !container.bulk_ingest_possible()) {
+				const bool q_bulk = has_q && w.quality_len_min == w.quality_len_max && container.bulk_ingest_possible_with_quality(q_len, true);
+				if (has_q ? !q_bulk : !container.bulk_ingest_possible(true)) {
 					// UMI quality strings (the container keeps them on the host): the records of this window come back as bytes and take the host
 					// reader's bulk path over them (fast_window: one quality row per read while the strings have one length), or, where that
 					// refuses, go record by record
@@ -1498,9 +1502,9 @@ void BamController::parse_bam_files(const std::vector<std::string> &bam_files, C
 					container.reserve_quality_rows(est_reads, q_len);
 					const uint8_t *rows = nullptr;
 					if (dropest_bam_decoder_quality_rows(dec, q_len, &rows)) throw std::runtime_error(std::string(dropest_bgzf_last_error()) + ": " + bam_name);
-					container.add_records_packed_device(w.d_cb, w.d_umi, w.d_gene, w.d_aux, size_t(w.n_accepted), any_gene, rows, q_len);
+					container.add_records_packed_device(w.d_cb, w.d_umi, w.d_gene, w.d_aux, size_t(w.n_accepted), any_gene, rows, q_len, target.device, target.stream);
 				} else
-					container.add_records_packed_device(w.d_cb, w.d_umi, w.d_gene, w.d_aux, size_t(w.n_accepted), any_gene);
+					container.add_records_packed_device(w.d_cb, w.d_umi, w.d_gene, w.d_aux, size_t(w.n_accepted), any_gene, target.device, target.stream);
 				host_ms[2] += since(t_phase);
 				_counters.cant_parse += size_t(w.counts[DROPEST_BAM_CANT_PARSE_NO_COUNT] + w.counts[DROPEST_BAM_CANT_PARSE]);
 				_counters.low_quality += size_t(w.counts[DROPEST_BAM_LOW_QUALITY]);

@@ -146,6 +146,7 @@ CellsDataContainer::CellsDataContainer(const std::shared_ptr<Merge::MergeStrateg
 	if (devices.size() == 1) { check(dropest_ctx_create(&cfg, &_ctx)); return; }
 	std::vector<int32_t> dev(devices.begin(), devices.end());
 	_shards.assign(devices.size(), nullptr);
+	_shard_devices = devices;
 	check(dropest_shard_group_create(&cfg, int32_t(dev.size()), dev.data(), _shards.data()));
 }
 
@@ -353,9 +354,10 @@ void CellsDataContainer::add_records_packed(const uint64_t *cb, const uint64_t *
 	}
 }
 
-void CellsDataContainer::add_records_packed_device(const uint64_t *d_cb, const uint64_t *d_umi, const uint32_t *d_gene, const uint32_t *d_aux, size_t n, bool any_gene) {
+void CellsDataContainer::add_records_packed_device(const uint64_t *d_cb, const uint64_t *d_umi, const uint32_t *d_gene, const uint32_t *d_aux, size_t n, bool any_gene,
+                                                   int src_device, void *stream) {
 	if (_is_initialized) throw std::runtime_error("Container is already initialized");
-	if (!bulk_ingest_possible()) throw std::runtime_error("add_records_packed: the container is sharded or carries UMI qualities (use add_record)");
+	if (!bulk_ingest_possible(true)) throw std::runtime_error("add_records_packed: the container carries UMI qualities (use add_record)");
 	_preview_valid = false; ++_generation;
 	if (!n) return;
 	flush();                                   // whatever add_record collected comes first
@@ -366,9 +368,10 @@ void CellsDataContainer::add_records_packed_device(const uint64_t *d_cb, const u
 	const auto t0 = std::chrono::steady_clock::now();
 	if (!_qual_lens.empty()) _qual_lens.insert(_qual_lens.end(), n, uint8_t(0));
 	const auto t1 = std::chrono::steady_clock::now();
-	send_side_strings(_ctx);
+	if (!sharded()) send_side_strings(_ctx);
 	const auto t2 = std::chrono::steady_clock::now();
-	check(dropest_push_reads_device(_ctx, d_cb, d_umi, d_gene, d_aux, n, 0));
+	if (sharded()) push_device_sharded(d_cb, d_umi, d_gene, d_aux, n, src_device, stream);
+	else check(dropest_push_reads_device(_ctx, d_cb, d_umi, d_gene, d_aux, n, 0));
 	if (trace) {
 		auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
 		std::fprintf(stderr, "[bam] container: %zu reads: quality lengths %.2f ms, side strings %.2f ms (%zu), push %.2f ms\n", n, ms(t0, t1), ms(t1, t2), _side.size(), ms(t2, std::chrono::steady_clock::now()));
@@ -376,9 +379,9 @@ void CellsDataContainer::add_records_packed_device(const uint64_t *d_cb, const u
 }
 
 void CellsDataContainer::add_records_packed_device(const uint64_t *d_cb, const uint64_t *d_umi, const uint32_t *d_gene, const uint32_t *d_aux, size_t n, bool any_gene,
-                                                   const uint8_t *quality_rows, size_t ql) {
+                                                   const uint8_t *quality_rows, size_t ql, int src_device, void *stream) {
 	if (_is_initialized) throw std::runtime_error("Container is already initialized");
-	if (!bulk_ingest_possible_with_quality(ql) || !quality_rows) throw std::runtime_error("add_records_packed: UMI quality strings of this length cannot be taken in bulk here (use add_record)");
+	if (!bulk_ingest_possible_with_quality(ql, true) || !quality_rows) throw std::runtime_error("add_records_packed: UMI quality strings of this length cannot be taken in bulk here (use add_record)");
 	_preview_valid = false; ++_generation;
 	if (!n) return;
 	flush();
@@ -390,8 +393,46 @@ void CellsDataContainer::add_records_packed_device(const uint64_t *d_cb, const u
 	if (_umi_quality_length == size_t(-1)) _qual_pending += n;
 	else _qual.insert(_qual.end(), quality_rows, quality_rows + n * ql);
 	_qual_reads += n;
+	if (sharded()) { push_device_sharded(d_cb, d_umi, d_gene, d_aux, n, src_device, stream); return; }   // (_qual is cut per shard from _shard_reads in set_initialized)
 	send_side_strings(_ctx);
 	check(dropest_push_reads_device(_ctx, d_cb, d_umi, d_gene, d_aux, n, 0));
+}
+
+std::vector<dropest_deal_piece> CellsDataContainer::deal(size_t n) const {
+	std::vector<dropest_deal_piece> pieces(_shards.size());
+	uint32_t k = 0;
+	check(dropest_deal_range(_dealt, n, std::max<size_t>(1, shard_quota), int32_t(_shards.size()), pieces.data(), &k));
+	pieces.resize(k);
+	return pieces;
+}
+
+void CellsDataContainer::send_new_side_strings_to_shards() {
+	if (_side.size() == _side_sent) return;
+	std::vector<const char *> ptrs(_side.size());
+	for (size_t i = 0; i < _side.size(); ++i) ptrs[i] = _side[i].c_str();
+	for (dropest_shard *s : _shards) check(dropest_set_side_strings(dropest_shard_ctx(s), ptrs.data(), ptrs.size()));
+	_side_sent = _side.size();
+}
+
+CellsDataContainer::IngestTarget CellsDataContainer::next_read_target() const {
+	IngestTarget t;
+	if (!sharded() || _shard_devices.size() != _shards.size()) { t.device = _device; t.stream = _ctx ? dropest_stream(_ctx) : nullptr; return t; }
+	const size_t shard = std::min<size_t>(_shards.size() - 1, size_t((_dealt + _cb.size()) / std::max<size_t>(1, shard_quota)));   // (the pending batch goes first)
+	t.device = _shard_devices[shard]; t.stream = dropest_stream(dropest_shard_ctx(_shards[shard]));
+	return t;
+}
+
+// A window of device columns on a sharded container (the pending batch is flushed by the caller): the strings met since the last push, then
+// every piece of the window to the shard its ordinals belong to, device to device.
+void CellsDataContainer::push_device_sharded(const uint64_t *d_cb, const uint64_t *d_umi, const uint32_t *d_gene, const uint32_t *d_aux, size_t n, int src_device, void *stream) {
+	if (src_device < 0) { const IngestTarget t = next_read_target(); src_device = t.device; stream = t.stream; }
+	send_new_side_strings_to_shards();
+	if (_shard_reads.size() != _shards.size()) _shard_reads.assign(_shards.size(), 0);
+	for (const dropest_deal_piece &p : deal(n)) {
+		check(dropest_shard_push_reads_device(_shards[size_t(p.shard)], d_cb + p.offset, d_umi + p.offset, d_gene + p.offset, d_aux + p.offset, p.count, _dealt + p.offset, int32_t(src_device), stream));
+		_shard_reads[size_t(p.shard)] += size_t(p.count);
+	}
+	_dealt += n;
 }
 
 void CellsDataContainer::set_reference_names(const std::vector<std::string> &names) {
@@ -507,22 +548,22 @@ void CellsDataContainer::note_quality_length(size_t ql) {
 
 void CellsDataContainer::flush() {
 	if (_cb.empty()) return;
-	std::vector<const char *> ptrs(_side.size());
-	for (size_t i = 0; i < _side.size(); ++i) ptrs[i] = _side[i].c_str();
 	if (sharded()) {
 		// Every shard holds ONE contiguous range of the stream, ascending with the shard: the first SHARD_QUOTA reads go to
 		// shard 0, the next to shard 1, ... (the stream's length is not known while it arrives; the pass re-distributes the
 		// reads by barcode owner anyway, so WHERE they wait only decides which PCIe link carried them).
-		if (_side.size() != _side_sent) { for (dropest_shard *s : _shards) check(dropest_set_side_strings(dropest_shard_ctx(s), ptrs.data(), ptrs.size())); _side_sent = _side.size(); }
-		const size_t shard = std::min<size_t>(_shards.size() - 1, size_t(_batches / std::max<size_t>(1, shard_quota / BATCH)));
-		check(dropest_shard_push_reads(_shards[shard], _cb.data(), _umi.data(), _gene.data(), _aux.data(), _cb.size(), _batches * BATCH));
+		// The batch -- a whole one, or what was pending when a window of device columns or set_initialized came -- starts at the running count.
+		send_new_side_strings_to_shards();
 		if (_shard_reads.size() != _shards.size()) _shard_reads.assign(_shards.size(), 0);
-		_shard_reads[shard] += _cb.size();
-		++_batches;
+		for (const dropest_deal_piece &p : deal(_cb.size())) {
+			check(dropest_shard_push_reads(_shards[size_t(p.shard)], _cb.data() + p.offset, _umi.data() + p.offset, _gene.data() + p.offset, _aux.data() + p.offset, p.count, _dealt + p.offset));
+			_shard_reads[size_t(p.shard)] += size_t(p.count);
+		}
+		_dealt += _cb.size();
 		_cb.clear(); _umi.clear(); _gene.clear(); _aux.clear();
 		return;
 	}
-	check(dropest_set_side_strings(_ctx, ptrs.data(), ptrs.size()));
+	send_side_strings(_ctx);
 	check(dropest_push_reads(_ctx, _cb.data(), _umi.data(), _gene.data(), _aux.data(), _cb.size()));
 	_cb.clear(); _umi.clear(); _gene.clear(); _aux.clear();
 }

@@ -286,7 +286,13 @@ private:
 	// the rest; expect_reads() sizes the quota so that the ranges come out even); merge_and_filter runs the sharded pass
 	// (include/dropest_amd.h: dropest_shard_*), one host thread per GPU
 	std::vector<dropest_shard *> _shards;
-	uint64_t _batches = 0;
+	std::vector<int> _shard_devices;          // HIP ordinal of every shard
+	uint64_t _dealt = 0;                      // reads dealt to the shards so far: the stream ordinal of the next one
+	bool _quota_fixed = false;                // set_shard_quota: expect_reads leaves the quota alone
+	// the pieces (shard, offset, count) a run of n reads at the running count falls into (dropest_deal_range: the one statement of the rule)
+	std::vector<dropest_deal_piece> deal(size_t n) const;
+	void send_new_side_strings_to_shards();
+	void push_device_sharded(const uint64_t *d_cb, const uint64_t *d_umi, const uint32_t *d_gene, const uint32_t *d_aux, size_t n, int src_device, void *stream);
 	size_t _side_sent = 0;
 	int _split_parts = 0;     // > 0: one device, the stream split over this many shards because the sort key passed 64 bits
 	void split_for_wide_keys();
@@ -346,7 +352,7 @@ private:
 
 public:
 	static const size_t BATCH = size_t(1) << 20;
-	size_t shard_quota = size_t(1) << 27;   // sharded container: reads (a multiple of BATCH) a shard takes before the next one starts
+	size_t shard_quota = size_t(1) << 27;   // sharded container: reads a shard takes before the next one starts
 	// A caller that knows roughly how many reads will come (a BAM's size, a previous run) says so before the first add_record: the
 	// quota becomes ceil(expected / shards) rounded up to whole batches, so that every GPU and every PCIe link carries its share
 	// (with the default quota a stream shorter than 2^27 reads lands on shard 0 alone and a very long one piles onto the last).
@@ -356,10 +362,23 @@ public:
 			if (_ctx && !_is_initialized && expected) (void)dropest_reserve_reads(_ctx, expected);
 			return;
 		}
-		if (_batches) return;
+		if (_dealt || _quota_fixed) return;
 		const size_t per = (expected + _shards.size() - 1) / _shards.size();
 		shard_quota = std::max<size_t>(BATCH, (per + BATCH - 1) / BATCH * BATCH);
 	}
+
+	// The quota as a number of reads, any positive one, fixed: expect_reads() does not change it any more.  Before the first read is dealt.
+	void set_shard_quota(size_t reads) {
+		if (!reads) throw std::runtime_error("set_shard_quota: a quota of 0 reads");
+		if (_dealt) throw std::runtime_error("set_shard_quota: reads have been dealt already");
+		shard_quota = reads; _quota_fixed = true;
+	}
+	// sharded container: reads dealt to every shard so far, in shard order (reads still waiting in the add_record batch are not counted)
+	const std::vector<size_t> &shard_reads() const { return _shard_reads; }
+	// Where the NEXT read of the stream will wait: the GPU, and the stream of the context there (one context: the container's own).  A reader that
+	// decodes on the device places its decoder there, lends it that stream, and names both when it hands its columns over.
+	struct IngestTarget { int device = 0; void *stream = nullptr; };
+	IngestTarget next_read_target() const;
 
 	CellsDataContainer(const std::shared_ptr<Merge::MergeStrategyAbstract> &merge_strategy,
 	                   const std::shared_ptr<Merge::UMIs::MergeUMIsStrategyAbstract> &umi_merge_strategy,
@@ -415,16 +434,23 @@ public:
 		for (auto const &kv : _gene_by_hash) { gene_hash.push_back(kv.first); gene_id.push_back(kv.second); }
 		chr_of_ref.assign(_ref_chr.begin(), _ref_chr.end());
 	}
-	// add_records_packed for columns that already live in the container's GPU memory (include/dropest_bgzf.h); any_gene: some read carries a gene
-	void add_records_packed_device(const uint64_t *d_cb, const uint64_t *d_umi, const uint32_t *d_gene, const uint32_t *d_aux, size_t n, bool any_gene);
-	// ... with one row of ql quality bytes per read in HOST memory (bulk_ingest_possible_with_quality(ql); every gene-bearing read's string is ql long)
-	void add_records_packed_device(const uint64_t *d_cb, const uint64_t *d_umi, const uint32_t *d_gene, const uint32_t *d_aux, size_t n, bool any_gene, const uint8_t *quality_rows, size_t ql);
+	// add_records_packed for columns that already live in the container's GPU memory (include/dropest_bgzf.h); any_gene: some read carries a gene.
+	// A sharded container takes them too (bulk_ingest_possible(true)): the pending add_record batch goes first, then the window is cut at the
+	// quota boundaries and every piece is appended to its shard's resident reads on the device (dropest_shard_push_reads_device).  There
+	// src_device / stream say where the columns live and which stream wrote them (-1: what next_read_target() names at the time of the call);
+	// one context ignores both.
+	void add_records_packed_device(const uint64_t *d_cb, const uint64_t *d_umi, const uint32_t *d_gene, const uint32_t *d_aux, size_t n, bool any_gene,
+	                               int src_device = -1, void *stream = nullptr);
+	// ... with one row of ql quality bytes per read in HOST memory (bulk_ingest_possible_with_quality(ql, true); every gene-bearing read's string is ql long)
+	void add_records_packed_device(const uint64_t *d_cb, const uint64_t *d_umi, const uint32_t *d_gene, const uint32_t *d_aux, size_t n, bool any_gene, const uint8_t *quality_rows, size_t ql,
+	                               int src_device = -1, void *stream = nullptr);
 	// ---- bulk ingest (the BAM reader's fast path) ----------------------------------------------------------------------
 	// add_record read by read costs a handful of vector appends and dictionary look-ups per read on ONE thread; a caller that
 	// parses records on many threads resolves the dictionaries itself -- the few reads per window that bring something new
 	// (an unseen gene name or chromosome, a barcode / UMI with N), in stream order, through the intern_* members -- and hands
 	// whole arrays of packed records over.  Same effect as add_record(ParsedRead) read by read, in the same order.
-	bool bulk_ingest_possible() const { return !sharded() && !_is_initialized && (_umi_quality_length == size_t(-1) || _umi_quality_length == 0); }
+	// (device_columns: the answer for add_records_packed_device, which a sharded container takes; the host-array overloads below need one context)
+	bool bulk_ingest_possible(bool device_columns = false) const { return (device_columns || !sharded()) && !_is_initialized && (_umi_quality_length == size_t(-1) || _umi_quality_length == 0); }
 	uint64_t intern_barcode(const std::string &s) { return encode(s, _side_cb); }
 	uint64_t intern_umi(const std::string &s) { return encode(s, _side_umi); }
 	uint32_t intern_gene(std::string_view name, uint64_t hash);
@@ -439,12 +465,12 @@ public:
 	// The same for reads with UMI quality strings of ONE length: quality[k] = counts-of-run-k rows of `ql` bytes (the row of a read without a gene is
 	// not looked at).  Allowed while every gene-bearing read so far had that length (bulk_ingest_possible_with_quality): what UMI::add_read's length
 	// check (UMI.cpp:26-28) needs beyond that goes through add_record.
-	bool bulk_ingest_possible_with_quality(size_t ql) const {
-		return !sharded() && !_is_initialized && !_mol_qlen_tracking && _qual_lens.empty() && ql > 0 && ql <= 255 && (_umi_quality_length == size_t(-1) || _umi_quality_length == ql);
+	bool bulk_ingest_possible_with_quality(size_t ql, bool device_columns = false) const {
+		return (device_columns || !sharded()) && !_is_initialized && !_mol_qlen_tracking && _qual_lens.empty() && ql > 0 && ql <= 255 && (_umi_quality_length == size_t(-1) || _umi_quality_length == ql);
 	}
 	void add_records_packed(const std::vector<PackedRun> &runs, const std::vector<const uint8_t *> &quality, size_t ql);
 	void reserve_quality_rows(size_t reads, size_t ql) { if (reads && ql && _qual.capacity() < reads * ql) _qual.reserve(reads * ql); }   // (a reader that knows how long the stream will be)
-	bool bulk_ingest_possible_at_all() const { return !sharded() && !_is_initialized && !_mol_qlen_tracking && _qual_lens.empty(); }   // (with or without quality rows: the window decides)
+	bool bulk_ingest_possible_at_all(bool device_columns = false) const { return (device_columns || !sharded()) && !_is_initialized && !_mol_qlen_tracking && _qual_lens.empty(); }   // (with or without quality rows: the window decides)
 	static bool pack_code(std::string_view s, uint64_t &code);
 	static uint64_t hash_name(std::string_view s);
 	void set_initialized();

@@ -2535,6 +2535,53 @@ dropest_status dropest_shard_push_reads(dropest_shard *s, const uint64_t *cb, co
 	});
 }
 
+dropest_status dropest_shard_push_reads_device(dropest_shard *s, const uint64_t *d_cb, const uint64_t *d_umi, const uint32_t *d_gene, const uint32_t *d_aux,
+                                               uint64_t n, uint64_t first_ordinal, int32_t src_device, void *stream) {
+	return guarded([&] {
+		if (!s) throw InvalidError("null shard");
+		if (!n) return;
+		if (!d_cb || !d_umi || !d_gene || !d_aux) throw InvalidError("null read array");
+		if (s->pushed.n + n >= 0xFFFFFFFEull) throw UnsupportedError("more than 2^32-2 reads per shard");
+		if (s->pushed.n != 0 && first_ordinal != s->first_ordinal + s->pushed.n) throw InvalidError("the batches pushed to a shard must continue its ordinal range without a gap");
+		const int dev = s->ctx->cfg.device;
+		const bool was_empty = s->pushed.n == 0;
+		if (src_device == dev) {
+			// (on the caller's stream: whatever wrote the columns there -- the BAM decoder's kernels and its patch -- is in front of the append)
+			HIP_CHECK(hipSetDevice(dev));
+			s->pushed.push_device(d_cb, d_umi, d_gene, d_aux, size_t(n), stream ? hipStream_t(stream) : s->ctx->stream);
+		} else {
+			// Columns of another GPU: their writers are waited for on that GPU, then four peer copies on this shard's own stream.  (Never run: every
+			// machine this was developed on has one GPU -- DESIGN section 7.)
+			int n_dev = 0;
+			HIP_CHECK(hipGetDeviceCount(&n_dev));
+			if (src_device < 0 || src_device >= n_dev) throw InvalidError("no such source device");
+			HIP_CHECK(hipSetDevice(src_device));
+			HIP_CHECK(stream ? hipStreamSynchronize(hipStream_t(stream)) : hipDeviceSynchronize());
+			HIP_CHECK(hipSetDevice(dev));
+			s->pushed.push_peer(d_cb, d_umi, d_gene, d_aux, size_t(n), dev, src_device, s->ctx->stream);
+		}
+		if (was_empty) s->first_ordinal = first_ordinal;
+	});
+}
+
+// Plain host code: the one statement of how a stream is dealt to shards (shard = min(n_shards - 1, ordinal / quota)).
+dropest_status dropest_deal_range(uint64_t first_ordinal, uint64_t n, uint64_t quota, int32_t n_shards, dropest_deal_piece *pieces_out, uint32_t *n_pieces_out) {
+	return guarded([&] {
+		if (!n_pieces_out || (n && !pieces_out)) throw InvalidError("null output");
+		if (!quota || n_shards <= 0) throw InvalidError("a quota and a number of shards above 0");
+		*n_pieces_out = 0;
+		if (first_ordinal + n < first_ordinal) throw InvalidError("the range passes 2^64");
+		uint64_t at = 0;
+		while (at < n) {
+			const uint64_t ord = first_ordinal + at, shard = std::min<uint64_t>(uint64_t(n_shards) - 1, ord / quota);
+			// the last shard takes whatever is left; the others end where ordinal / quota changes
+			const uint64_t count = shard + 1 == uint64_t(n_shards) ? n - at : std::min<uint64_t>(n - at, quota - ord % quota);
+			pieces_out[(*n_pieces_out)++] = dropest_deal_piece{shard, at, count};
+			at += count;
+		}
+	});
+}
+
 dropest_status dropest_shard_set_umi_qualities(dropest_shard *s, const uint8_t *qualities, uint32_t quality_length, uint64_t n_reads) {
 	return guarded([&] {
 		if (!s) throw InvalidError("null shard");

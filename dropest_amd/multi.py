@@ -61,6 +61,14 @@ class Shard:
         arrs = [np.ascontiguousarray(a, dt) for a, dt in ((cb, np.uint64), (umi, np.uint64), (gene, np.uint32), (aux, np.uint32))]
         self._chk(self.L.dropest_shard_push_reads(self.h, *[a.ctypes.data for a in arrs], len(arrs[0]), int(first_ordinal)))
 
+    def push_device(self, arrays, first_ordinal, offset=0, n=None, stream=None):
+        """Reads [offset, offset + n) of `arrays` (capi.DeviceArrays on any GPU) appended to what push_reads fills (see
+        dropest_shard_push_reads_device); the arrays are free again when this returns.  stream: a hipStream_t of the arrays' device
+        that their writer ran on (None: the shard context's own stream)."""
+        n = arrays.n - offset if n is None else n
+        ptrs = [C.c_void_p((p.value or 0) + offset * w) for p, w in zip(arrays.ptrs, (8, 8, 4, 4))]
+        self._chk(self.L.dropest_shard_push_reads_device(self.h, *ptrs, int(n), int(first_ordinal), int(arrays.device), stream))
+
     def set_side_strings(self, strings):
         self.ctx.set_side_strings(strings)
 

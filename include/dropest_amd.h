@@ -535,6 +535,20 @@ dropest_status dropest_shard_set_reads_device(dropest_shard *shard, const uint64
  * that does not know the stream's length fills shard 0 up to a quota, then shard 1, ...: the exchange spreads the work). */
 dropest_status dropest_shard_push_reads(dropest_shard *shard, const uint64_t *cb, const uint64_t *umi, const uint32_t *gene,
                                         const uint32_t *aux, uint64_t n, uint64_t first_ordinal);
+/* The same from DEVICE memory (the BAM decoder's dense columns): n reads appended to the store dropest_shard_push_reads fills, with the same
+ * checks (null arrays, 2^32-2 reads per shard, first_ordinal continuing the shard's range: DROPEST_ERR_INVALID otherwise, and nothing
+ * changes).  Host and device pushes may follow one another on one shard.  src_device = the GPU the columns live on.  The shard's own: one
+ * append kernel on `stream` (a hipStream_t of that GPU, NULL = the shard context's), so whatever wrote the columns on that stream is in
+ * front of it.  Another GPU: `stream` (of src_device; NULL = all of that device) is waited for, then hipMemcpyPeerAsync on the shard's
+ * stream.  Either way the call returns when the reads are in the store: the caller's columns may be overwritten. */
+dropest_status dropest_shard_push_reads_device(dropest_shard *shard, const uint64_t *d_cb, const uint64_t *d_umi, const uint32_t *d_gene,
+                                               const uint32_t *d_aux, uint64_t n, uint64_t first_ordinal, int32_t src_device, void *stream);
+/* How a feeder deals the stream: shard of a read = min(n_shards - 1, ordinal / quota).  The run of n reads that starts at first_ordinal
+ * falls into *n_pieces_out <= n_shards pieces, in stream order: reads [offset, offset + count) of the run go to `shard`.  pieces_out has
+ * room for n_shards entries.  n = 0: no piece.  Plain host code (no device is touched). */
+typedef struct dropest_deal_piece { uint64_t shard, offset, count; } dropest_deal_piece;
+dropest_status dropest_deal_range(uint64_t first_ordinal, uint64_t n, uint64_t quota, int32_t n_shards, dropest_deal_piece *pieces_out,
+                                  uint32_t *n_pieces_out);
 /* UMI quality strings of the shard's resident reads (see dropest_set_umi_qualities): quality_length bytes per read, in the order the reads
  * were pushed / set; call on EVERY shard of the run (a shard without reads: n_reads = 0), same length everywhere, before
  * dropest_shard_step.  The strings travel with their reads in the exchange; the sums are accumulated where the cell lives and follow
