@@ -459,7 +459,7 @@ struct dropest_ctx {
 
 	// scratch
 	dropest::DevBuf<u32> tile_counts, tile_prefix, scalars, rs_hist, rs_row_total, rs_digit_base;
-	dropest::DevBuf<u32> real_list, m_col_cell, m_col_start;
+	dropest::DevBuf<u32> real_list;
 	dropest::DevBuf<dropest::CellRowPod> real_rows_dev;
 	dropest::DevBuf<u32> sizes_dev;
 	bool real_list_current = false;          // real_list holds the ids of `real`, in order
@@ -469,19 +469,35 @@ struct dropest_ctx {
 	struct MatrixResult {
 		dropest::DevBuf<u32> d_row, d_val;
 		dropest::PinnedBuf<u32> h_row, h_val;
-		// the narrow form (dropest_count_matrix_csc_narrow): 16-bit rows / values, [0] overflow count, then positions, then values
+		// A list of the entries a narrow form cannot hold, on the device and (pinned) on the host: [0] their count, then `cap` positions, then
+		// `cap` values.  The emit kernels and matrix_lists_out*_kernel (k_misc.h) fill and move this layout; it is spelled out here only.
+		struct List {
+			dropest::DevBuf<u32> d;
+			dropest::PinnedBuf<u32> h;
+			u32 cap = 0, n = 0;   // capacity of the last emit; entries of it that have arrived on the host
+			void ensure(u32 c, bool to_host) { cap = c; d.ensure(1 + 2 * size_t(c)); if (to_host) h.ensure(1 + 2 * size_t(c)); }
+			u32 *d_count() const { return d.p; }
+			u32 *d_pos() const { return d.p + 1; }
+			u32 *d_val() const { return d.p + 1 + cap; }
+			u32 *h_count() const { return h.p; }
+			u32 *h_pos() const { return h.p ? h.p + 1 : nullptr; }
+			u32 *h_val() const { return h.p ? h.p + 1 + cap : nullptr; }
+		};
+		// the narrow form (dropest_count_matrix_csc_narrow): 16-bit rows / values and the list of the values beyond them
 		dropest::DevBuf<uint16_t> d_row16, d_val16;
 		dropest::PinnedBuf<uint16_t> h_row16, h_val16;
-		dropest::DevBuf<u32> d_ovf;
-		dropest::PinnedBuf<u32> h_ovf;
+		List vals;
 		// the byte form (dropest_count_matrix_csc_bytes): row deltas / values of one byte, the value list above and a second list of exact rows
 		dropest::DevBuf<uint8_t> d_drow8, d_val8;
 		dropest::PinnedBuf<uint8_t> h_drow8, h_val8;
-		dropest::DevBuf<u32> d_rovf;
-		dropest::PinnedBuf<u32> h_rovf;
+		List rows;
 		int narrow = 0;                 // the form of the last emit as the caller sees it: 0 32-bit, 1 16-bit, 2 bytes
-		u32 n_ovf = 0, n_rovf = 0;
-		u32 rcap = 0, vcap = 0;         // capacities of the row / value lists of the last byte-form emit
+		// The columns of the slot's last emit on the device: cell id and first entry of each, and the order the byte-form kernels take them in
+		// (col_list_host: the host side of that asynchronous upload).  A rider's kernel (emit_rider, on `stream`) reads cm_raw's d_col_cell /
+		// d_col_start behind ev_raw_cols.  Whatever rewrites slot 1's arrays calls invalidate_prefetch() first -- no later rider is planned on
+		// them -- and writes them on `stream`, behind a rider already enqueued there, or on stream2 behind ev_fork (prefetch_raw_matrix).
+		dropest::DevBuf<u32> d_col_cell, d_col_start, d_col_list;
+		std::vector<u32> col_list_host;
 		// 32-bit slots that travel as bytes (matrix_decode.h): the chunked copy's events and the job that widens into h_row / h_val
 		bool wire = false;
 		std::shared_ptr<dropest::DecodeJob> job, late_job;   // late_job: finished, but a decoding thread may not have left it yet
@@ -761,7 +777,10 @@ struct dropest_ctx {
 	void sort_filtered(u32 genes_threshold, int max_cells);
 	void emit_matrix(bool filtered_m, bool reads_output, bool to_host = true, int form = 0, bool direct = false);
 	bool narrow_possible() const;
+	// the source side of an emit launch for slot M: its column arrays, the (cell, gene) tables and the value array of (filtered, reads)
+	dropest::MatrixArgs matrix_source(const MatrixResult &M, bool filtered_m, bool reads_output) const;
 	void matrix_outputs(MatrixResult &M, uint64_t nnz, int form, bool to_host, dropest::MatrixArgs &a);
+	void launch_emit(int dev_form, dropest::MatrixArgs a, MatrixResult &M, hipStream_t st);   // the emit kernel(s) of a device form over M.colptr's columns
 	void matrix_copy_out(MatrixResult &M, uint64_t nnz, hipStream_t st);
 	void matrix_finish_overflow(MatrixResult &M, hipStream_t st);
 	// 32-bit slots over the wire as bytes: true when this matrix takes that way (large enough, not switched off)
@@ -786,9 +805,9 @@ struct dropest_ctx {
 	hipStream_t stream2 = nullptr;
 	hipEvent_t ev_fork = nullptr, ev_raw = nullptr, ev_raw_cols = nullptr;   // ev_raw_cols: cm_raw's column arrays are on the device (a rider's emit reads them)
 	bool emit_rider(bool reads_output, const std::vector<u32> &col_cell, uint64_t nnz);
-	dropest::DevBuf<u32> m2_col_cell, m2_col_start, m2_col_list, m_col_list;
-	std::vector<u32> m2_col_list_host, m_col_list_host;   // (host sides of asynchronous uploads: kept with the context)
-	void launch_emit_bytes(dropest::MatrixArgs a, const std::vector<u32> &rows_per_column, dropest::DevBuf<u32> &list, std::vector<u32> &host_list, hipStream_t st);
+	// after the byte-form kernels on `st`: the chunked copies of d_a / d_b to h_a / h_b (chunks of job->chunk_end over `colptr`) and the pool's job
+	void start_decode_job(MatrixResult &M, const std::shared_ptr<dropest::DecodeJob> &job, const u32 *colptr, const uint8_t *d_a, const uint8_t *d_b,
+	                      uint8_t *h_a, uint8_t *h_b, hipStream_t st);
 	void prefetch_raw_matrix(bool reads_output, int form = 0, const dropest::CellRowPod *rows = nullptr, const dropest::u32 *ids = nullptr,
 	                         dropest::u32 count = 0);   // form: 0 32-bit, 1 16-bit, 2 bytes; rows / ids: the real cells as fetch_real_cells just received them
 	int auto_pf_form = -1;          // dropest_set_raw_matrix_prefetch: the form cm_raw will be asked for (-1: not announced)

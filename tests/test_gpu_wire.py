@@ -129,3 +129,35 @@ def test_cm_rides_on_cm_raw(kind, monkeypatch):
         if kind == "max_cells":
             assert len(cm[0]) - 1 == 150 and len(raw[0]) - 1 > 300
     c.close()
+
+
+def test_a_rewrite_of_cm_raws_slot_behind_a_rider_changes_nothing():
+    """Every matrix slot owns the column arrays its kernels read.  A rider's kernel reads cm_raw's: here cm is taken as a rider, then -- on the
+    same context, without a reset -- cm_raw of the other value kind rewrites its slot, cm_raw of the first kind rewrites it again, and cm is
+    made once more (now by its own byte form: the prefetch it rode on is gone).  All four must be what a fresh context gives directly."""
+    s = SynthStream(n_reads=4_000_000, n_cells=400, n_genes=20000)
+    reads = parity.canonical_stream(*s.generate_host())
+    kw = dict(min_genes_before_merge=20, min_genes_after_merge=100)
+
+    def take(c, filtered, reads_output):
+        return [x.copy() for x in c.count_matrix_csc(filtered=filtered, reads_output=reads_output)]
+
+    c = capi.Context(**kw)
+    c.push_reads(*reads)
+    c.set_profiling(True)
+    c.set_raw_matrix_prefetch(0, False)
+    c.set_initialized(); c.merge_and_filter()
+    order = [(True, False), (False, True), (False, False), (True, False)]
+    got = [take(c, f, r) for f, r in order]
+    assert c.kernel_stats().get("count:cm_rides_on_cm_raw", {"launches": 0})["launches"] >= 1
+    c.close()
+
+    d = capi.Context(**kw)
+    d.push_reads(*reads)
+    d.set_matrix_wire(False)
+    d.set_initialized(); d.merge_and_filter()
+    want = {key: take(d, *key) for key in set(order)}
+    d.close()
+    assert len(want[(True, False)][1]) >= (1 << 18)      # cm itself is large enough for the wire
+    for key, g in zip(order, got):
+        assert all(np.array_equal(x, y) and x.dtype == y.dtype for x, y in zip(g, want[key])), key
