@@ -284,13 +284,13 @@ void dropest_ctx::build_merge_pairs(const std::vector<u32> &cells, MergeSearch &
 		size_t mine = 0; bool over = false;
 		for (size_t f = b; f < e; ++f) {
 			if (S.cnt[f] > u32(WL_CAND_CAP)) { over = true; continue; }
-			bool self = false;
+			u32 self = 0;   // (a whitelist line that repeats an entry lists the base more than once)
 			for (u32 k = 0; k < S.cnt[f]; ++k)
-				if (S.fcell[S.off[f] + k] == cells[f]) { self = true; S.self_ridx[f] = S.fridx[S.off[f] + k]; }
+				if (S.fcell[S.off[f] + k] == cells[f]) { ++self; S.self_ridx[f] = S.fridx[S.off[f] + k]; }
 			// the base is itself a whitelist barcode: neighbour_cells[0] == base (RealBarcodesMergeStrategy.cpp:34-35) ends the
 			// decision there; the Poisson estimator goes on to its other neighbours (PoissonTargetEstimator.cpp:26-29)
 			u32 np = 0;
-			if (!(self && cfg.merge_kind != DROPEST_MERGE_POISSON_REAL)) np = S.cnt[f] - (self ? 1u : 0u);
+			if (!(self && cfg.merge_kind != DROPEST_MERGE_POISSON_REAL)) np = S.cnt[f] - self;
 			n_pairs[f] = np; mine += np;
 		}
 		per_worker[w] = mine;

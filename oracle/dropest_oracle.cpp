@@ -272,7 +272,7 @@ struct Whitelist {
 			r.push_back(cb.substr(cb.size() - bc2_length));
 		} else {                // ConstLengthBarcodesParser.cpp:33-48
 			if (cb.size() != total_length)
-				throw std::runtime_error("Barcode '" + cb + "' has wrong length");
+				throw std::runtime_error("Barcode '" + cb + "' has wrong length (" + std::to_string(total_length) + " expected)");
 			size_t pos = 0;
 			for (size_t l : part_lengths) { r.push_back(cb.substr(pos, l)); pos += l; }
 		}
