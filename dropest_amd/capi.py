@@ -127,6 +127,7 @@ def lib():
         "dropest_poisson_intersection_prob": (C.c_int, [vp, C.c_uint64, C.c_uint64, u64p, P(C.c_double), P(C.c_double)]),
         "dropest_umi_distribution": (C.c_int, [vp, u64p, vp, vp]),
         "dropest_collisions_adjusted_sizes": (C.c_int, [C.c_int, vp, C.c_uint64, C.c_uint64, vp]),
+        "dropest_poisson_upper_tail": (C.c_int, [C.c_int64, C.c_double, P(C.c_double)]),
         "dropest_owner_of": (C.c_uint32, [C.c_uint64, C.c_uint32]),
         "dropest_partition_by_owner": (C.c_int, [C.c_int, vp, vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp, vp, vp, vp, vp, vp,
                                                  C.c_uint64]),
@@ -226,7 +227,7 @@ EXPORTED_SYMBOLS = [
     "dropest_count_matrix_csc", "dropest_count_matrix_csc_levels", "dropest_owner_of", "dropest_partition_by_owner", "dropest_partition_scratch_bytes", "dropest_clear_reads",
     "dropest_count_matrix_device", "dropest_cell_first_reads_device", "dropest_assemble_columns", "dropest_assemble_columns_async",
     "dropest_real_candidate_rows", "dropest_dev_copy_device", "dropest_umi_distribution",
-    "dropest_collisions_adjusted_sizes", "dropest_poisson_intersection_prob",
+    "dropest_collisions_adjusted_sizes", "dropest_poisson_intersection_prob", "dropest_poisson_upper_tail",
     "dropest_set_umi_qualities", "dropest_umi_quality_length", "dropest_cell_molecule_qualities",
     "dropest_set_umi_qualities_var", "dropest_cell_molecule_quality_lengths",
     "dropest_exclude_cell", "dropest_merge_cells", "dropest_merge_umis",
@@ -784,8 +785,20 @@ def radix_plan(varying_mask):
     return [(int(sh[i]), int(bt[i])) for i in range(n.value)]
 
 
+COLLISIONS_DIVERGED = 0xFFFFFFFFFFFFFFFF
+
+
+def poisson_upper_tail(k, lam):
+    """P(X >= k), X ~ Poisson(lam), as the -M merges evaluate it (host arithmetic, no GPU)."""
+    out = C.c_double()
+    rc = lib().dropest_poisson_upper_tail(int(k), float(lam), C.byref(out))
+    if rc != 0:
+        raise DropestError(rc, lib().dropest_last_error().decode())
+    return out.value
+
+
 def collisions_adjusted_sizes(probs, max_expression, device=0):
-    """Tools::CollisionsAdjuster table on the device."""
+    """Tools::CollisionsAdjuster table on the device; COLLISIONS_DIVERGED from the entry where the recurrence diverges."""
     p = np.ascontiguousarray(probs, np.float64)
     out = np.zeros(max_expression, np.uint64)
     rc = lib().dropest_collisions_adjusted_sizes(device, p.ctypes.data, len(p), max_expression, out.ctypes.data)

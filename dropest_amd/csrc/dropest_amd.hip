@@ -2640,14 +2640,18 @@ dropest_status dropest_collisions_adjusted_sizes(int device, const double *umi_p
                                                  uint64_t *adjusted_sizes) {
 	return guarded([&] {
 		if (!umi_probabilities || !adjusted_sizes) throw InvalidError("null argument");
-		HIP_CHECK(hipSetDevice(device));
 		if (max_expression == 0) return;
+		if (n == 0) {   // no UMI: new_prob = 0 at every step, nothing collides
+			for (uint64_t s = 1; s <= max_expression; ++s) adjusted_sizes[s - 1] = s;
+			return;
+		}
+		HIP_CHECK(hipSetDevice(device));
 		DevBuf<double> d_p, d_np, d_partial; DevBuf<CollisionState> d_st; DevBuf<u64> d_adj;
 		d_p.alloc(n); d_np.alloc(n); d_partial.alloc(CA_BLOCKS); d_st.alloc(1); d_adj.alloc(max_expression);
 		std::vector<double> ones(n, 1.0);
 		HIP_CHECK(hipMemcpy(d_p.p, umi_probabilities, n * 8, hipMemcpyHostToDevice));
 		HIP_CHECK(hipMemcpy(d_np.p, ones.data(), n * 8, hipMemcpyHostToDevice));
-		CollisionState st{0.0, 0ull, 0ull};
+		CollisionState st{0.0, 0ull, 0ull, 0ull};
 		HIP_CHECK(hipMemcpy(d_st.p, &st, sizeof(st), hipMemcpyHostToDevice));
 		hipLaunchKernelGGL(collisions_finish_kernel, dim3(1), dim3(1), 0, nullptr, d_partial.p, d_st.p, 0ull, d_adj.p);   // exponent of s = 1
 		for (uint64_t s = 1; s <= max_expression; ++s) {
@@ -2656,6 +2660,13 @@ dropest_status dropest_collisions_adjusted_sizes(int device, const double *umi_p
 		}
 		HIP_CHECK(hipGetLastError());
 		HIP_CHECK(hipMemcpy(adjusted_sizes, d_adj.p, max_expression * 8, hipMemcpyDeviceToHost));
+	});
+}
+
+dropest_status dropest_poisson_upper_tail(int64_t k, double lambda, double *out) {
+	return guarded([&] {
+		if (!out) throw InvalidError("null argument");
+		*out = poisson_upper_tail(long(k), lambda);
 	});
 }
 

@@ -8,6 +8,11 @@
 // map + reduction over the UMIs.  Double precision, no FMA contraction (the library is built with
 // -ffp-contract=off); the reduction order is fixed: per thread a strided left-to-right sum, then a wave shuffle
 // tree, then waves and blocks in index order.
+//
+// Divergence.  Once a size comes near the number of distinct UMIs, 1 - new_prob reaches 0 and sum_collisions leaves
+// every range (the reference's fpow then gets a negative exponent and does not terminate).  Both tables (the per-UMI
+// one here, the per-class one of poisson_merge.h) use collisions_diverged() and write COLLISIONS_DIVERGED into the
+// entry where that happens and into every entry after it; the entries before it are the reference's.
 #pragma once
 
 #include "util.h"
@@ -18,7 +23,16 @@ struct CollisionState {
 	double sum_collisions;
 	unsigned long long last_total;
 	unsigned long long delta;      // exponent of the current step
+	unsigned long long diverged;   // set at the first diverged step; every later step does no work (delta = 0)
 };
+
+constexpr unsigned long long COLLISIONS_DIVERGED = ~0ull;
+
+// step s just added 1 / one_minus - 1 to sum_collisions: the recurrence has left its domain when nothing was left of
+// 1 - new_prob, or when the total size of step s + 1 would pass 2^32
+__host__ __device__ inline bool collisions_diverged(double one_minus, unsigned long long s, double sum_collisions) {
+	return !(one_minus > 0) || !(sum_collisions < 4294967296.0) || s + 1 + (unsigned long long)sum_collisions > (1ull << 32);
+}
 
 __device__ inline double dev_fpow(double base, unsigned long long exp) {   // Tools::fpow, UtilFunctions.cpp:13-30
 	if (exp == 1) return base;
@@ -60,12 +74,18 @@ __global__ __launch_bounds__(CA_THREADS) void collisions_step_kernel(const doubl
 __global__ void collisions_finish_kernel(const double *__restrict__ partial, CollisionState *st, unsigned long long s,
                                          unsigned long long *__restrict__ adjusted) {
 	if (threadIdx.x || blockIdx.x) return;
-	if (s > 0) {
+	if (s > 0 && !st->diverged) {
 		double new_prob = 0;
 		for (int b = 0; b < CA_BLOCKS; ++b) new_prob += partial[b];
 		const double collision_num = 1.0 / (1.0 - new_prob) - 1.0;
 		st->sum_collisions += collision_num;
-		adjusted[s - 1] = (unsigned long long)lround(double(s) + st->sum_collisions);
+		if (collisions_diverged(1.0 - new_prob, s, st->sum_collisions)) st->diverged = 1;
+		else adjusted[s - 1] = (unsigned long long)lround(double(s) + st->sum_collisions);
+	}
+	if (st->diverged) {
+		if (s > 0) adjusted[s - 1] = COLLISIONS_DIVERGED;
+		st->delta = 0;
+		return;
 	}
 	const unsigned long long next_total = (s + 1) + (unsigned long long)st->sum_collisions;
 	st->delta = next_total - st->last_total;

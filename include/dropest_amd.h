@@ -333,9 +333,19 @@ dropest_status dropest_umi_distribution(dropest_ctx *ctx, uint64_t *n, uint64_t 
  * device in double precision, one launch pair per s (the recurrence over s is sequential); the inner sum over the
  * UMIs is a FIXED-ORDER parallel reduction, so results are reproducible run to run but may differ from the
  * reference's left-to-right sum in the last bits of `new_umi_prob` (the table itself is integer, after lround).
- * The reference pins this component only to 1e-2 (Tests/TestEstimationMergeProbs.cpp:113-140). */
+ * The reference pins this component only to 1e-2 (Tests/TestEstimationMergeProbs.cpp:113-140).
+ * Divergence: once the size comes near the number of distinct UMIs nothing is left of 1 - new_umi_prob, or the total size
+ * of the next step passes 2^32 (the reference's fpow then gets a negative exponent and does not terminate).  The entry
+ * where that happens and every entry after it are UINT64_MAX; the entries before it are the reference's and the call
+ * returns DROPEST_OK.  The -M merges build their table by the same rule and refuse such a container (UNSUPPORTED).
+ * n = 0 (no UMI, nothing collides): adjusted_size[s-1] = s.  max_expression = 0: nothing is written.  Neither launches
+ * anything. */
 dropest_status dropest_collisions_adjusted_sizes(int device, const double *umi_probabilities, uint64_t n,
                                                  uint64_t max_expression, uint64_t *adjusted_sizes);
+/* P(X >= k) for X ~ Poisson(lambda): what Rcpp::ppois(k - 1, lambda, false) returns (PoissonTargetEstimator.cpp:88), the
+ * function every -M probability goes through.  1 for k <= 0, 0 for lambda <= 0 (and k > 0).  Host arithmetic: no device
+ * is touched. */
+dropest_status dropest_poisson_upper_tail(int64_t k, double lambda, double *out);
 
 /* PoissonTargetEstimator::estimate_intersection_prob (PoissonTargetEstimator.cpp:67-94; the reference's tests call
  * it directly, Tests/TestEstimationMergeProbs.cpp:93-111) for two cells of the un-merged container: the UMI-gene
