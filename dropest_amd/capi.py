@@ -57,6 +57,20 @@ CELL_ROW_DTYPE = np.dtype([
 assert CELL_ROW_DTYPE.itemsize == C.sizeof(CellRow)
 
 
+class ValidationOpts(C.Structure):
+    """dropest_validation_opts (include/dropest_amd.h); 0 = the default."""
+    _fields_ = [("max_draws", C.c_uint64), ("round_candidates", C.c_uint64), ("max_keys_per_chunk", C.c_uint64)]
+
+
+class ValidationSample(C.Structure):
+    """dropest_validation_sample (include/dropest_amd.h)."""
+    _fields_ = [("min_ed", C.c_uint32), ("max_ed", C.c_uint32), ("n_pairs", C.c_uint64), ("cell1", C.c_void_p), ("cell2", C.c_void_p),
+                ("umis1", C.c_void_p), ("umis2", C.c_void_p), ("edit_distance", C.c_void_p), ("intersection", C.c_void_p),
+                ("expected", C.c_void_p), ("probability", C.c_void_p), ("n_found", C.c_uint64), ("draws_used", C.c_uint64),
+                ("complete", C.c_int32), ("rounds", C.c_uint32), ("chunks", C.c_uint32), ("reserved", C.c_uint32),
+                ("ms_view", C.c_double), ("ms_sampler", C.c_double), ("ms_evaluation", C.c_double)]
+
+
 class KernelStat(C.Structure):
     _fields_ = [("name", C.c_char_p), ("launches", C.c_uint32), ("ms", C.c_double), ("bytes", C.c_double)]
 
@@ -125,6 +139,9 @@ def lib():
         "dropest_umi_quality_length": (C.c_int, [vp, P(C.c_uint32)]),
         "dropest_cell_molecule_qualities": (C.c_int, [vp, C.c_uint64, C.c_uint64, vp]),
         "dropest_poisson_intersection_prob": (C.c_int, [vp, C.c_uint64, C.c_uint64, u64p, P(C.c_double), P(C.c_double)]),
+        "dropest_merge_validation": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint64, P(ValidationOpts), vp, vp, vp, vp, vp, vp, vp, vp, u64p, u64p,
+                                               P(C.c_int32)]),
+        "dropest_merge_validation_samples": (C.c_int, [vp, P(ValidationOpts), P(ValidationSample), C.c_uint32]),
         "dropest_umi_distribution": (C.c_int, [vp, u64p, vp, vp]),
         "dropest_collisions_adjusted_sizes": (C.c_int, [C.c_int, vp, C.c_uint64, C.c_uint64, vp]),
         "dropest_poisson_upper_tail": (C.c_int, [C.c_int64, C.c_double, P(C.c_double)]),
@@ -228,6 +245,7 @@ EXPORTED_SYMBOLS = [
     "dropest_count_matrix_device", "dropest_cell_first_reads_device", "dropest_assemble_columns", "dropest_assemble_columns_async",
     "dropest_real_candidate_rows", "dropest_dev_copy_device", "dropest_umi_distribution",
     "dropest_collisions_adjusted_sizes", "dropest_poisson_intersection_prob", "dropest_poisson_upper_tail",
+    "dropest_merge_validation", "dropest_merge_validation_samples",
     "dropest_set_umi_qualities", "dropest_umi_quality_length", "dropest_cell_molecule_qualities",
     "dropest_set_umi_qualities_var", "dropest_cell_molecule_quality_lengths",
     "dropest_exclude_cell", "dropest_merge_cells", "dropest_merge_umis",
@@ -707,6 +725,39 @@ class Context:
         n, e, p = C.c_uint64(), C.c_double(), C.c_double()
         self._chk(self.L.dropest_poisson_intersection_prob(self.h, cell1, cell2, C.byref(n), C.byref(e), C.byref(p)))
         return n.value, e.value, p.value
+
+    def merge_validation(self, *samples, max_draws=0, round_candidates=0, max_keys_per_chunk=0):
+        """MergeProbabilityValidator::run_validation for every (min_ed, max_ed, n_pairs) of `samples`, over one view of the current
+        molecules and one set of estimator tables (dropest_merge_validation_samples; one sample goes through dropest_merge_validation).
+        Returns one dict per sample (the dict itself for a single sample): cell1, cell2, umis1, umis2, edit_distance, intersection,
+        expected, probability (arrays of n_found entries), n_found, draws_used, complete, rounds, chunks, ms_view / _sampler / _evaluation."""
+        if len(samples) == 3 and not isinstance(samples[0], (tuple, list)):
+            samples = (tuple(samples),)
+        opts = ValidationOpts(max_draws, round_candidates, max_keys_per_chunk)
+        kinds = (("cell1", np.uint64), ("cell2", np.uint64), ("umis1", np.uint32), ("umis2", np.uint32), ("edit_distance", np.uint32),
+                 ("intersection", np.uint32), ("expected", np.float64), ("probability", np.float64))
+        arrays = [{k: np.zeros(max(1, n), t) for k, t in kinds} for _, _, n in samples]
+        if len(samples) == 1:
+            (lo, hi, n), a = samples[0], arrays[0]
+            found, draws, complete = C.c_uint64(), C.c_uint64(), C.c_int32()
+            self._chk(self.L.dropest_merge_validation(self.h, lo, hi, n, C.byref(opts), *[a[k].ctypes.data for k, _ in kinds],
+                                                      C.byref(found), C.byref(draws), C.byref(complete)))
+            out = {k: a[k][:found.value] for k, _ in kinds}
+            out.update(n_found=found.value, draws_used=draws.value, complete=complete.value)
+            return out
+        S = (ValidationSample * len(samples))()
+        for s, (lo, hi, n), a in zip(S, samples, arrays):
+            s.min_ed, s.max_ed, s.n_pairs = lo, hi, n
+            for k, _ in kinds:
+                setattr(s, k, a[k].ctypes.data)
+        self._chk(self.L.dropest_merge_validation_samples(self.h, C.byref(opts), S, len(samples)))
+        outs = []
+        for s, a in zip(S, arrays):
+            out = {k: a[k][:s.n_found] for k, _ in kinds}
+            out.update(n_found=int(s.n_found), draws_used=int(s.draws_used), complete=int(s.complete), rounds=int(s.rounds),
+                       chunks=int(s.chunks), ms_view=s.ms_view, ms_sampler=s.ms_sampler, ms_evaluation=s.ms_evaluation)
+            outs.append(out)
+        return outs
 
     def sort_layout(self):
         out = (C.c_uint32 * 7)()

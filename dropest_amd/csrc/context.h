@@ -659,6 +659,29 @@ struct dropest_ctx {
 	// the estimator's tables (poisson_merge.h): built from the UMI counts of this context, or of all shards (merge_shard.h)
 	struct PoissonTables { dropest::DevBuf<double> p, mult, np; dropest::DevBuf<u64> adj; u32 n_classes = 0, max_size = 0; bool ready = false; } ptab;
 	void poisson_local_umis(u32 &kept, u32 &max_size);
+	// table building and per-pair evaluation as separate steps (poisson_expected_intersections runs one after the other)
+	struct PoissonSource { const u32 *cell_cg_begin, *cell_cg_count; const u64 *cg_key; const u32 *cg_mol_begin; u64 gene_mask; };
+	void poisson_tables_from_state();
+	void poisson_tables_from_umi_codes(u32 kept, u64 code_mask, u32 max_size);
+	void poisson_expected_pairs(const PoissonSource &src, const u32 *d_pb, const u32 *d_pc, u32 NP, const u32 *count_host, double *expected);
+	// merge validation statistics, -S (validation.h): the filtered cells' molecules as they are NOW (groups the UMI merge rewrote included), keyed
+	// rank in filtered_cells() | gene | UMI field, sorted, with the (cell, gene) and per-cell tables the pair kernels read
+	struct ValidationView {
+		dropest::DevBuf<u64> mol_key, cg_key;
+		dropest::DevBuf<u32> cg_mol_begin, cell_cg_begin, cell_cg_count;
+		dropest::DevBuf<uint4> barcodes;              // [F] rows of VAL_STRIDE bytes (k_validation.h)
+		std::vector<uint64_t> cells;                  // filtered_cells()
+		std::vector<u32> umis;                        // their TOTAL_UMIS stat
+		u32 n_mol = 0, n_cg = 0, F = 0;
+		int umi_bits = 0;
+		double ms = 0;
+	};
+	bool is_shard_ctx = false, was_split = false;     // contexts the validation refuses
+	void validation_build_view(ValidationView &V);
+	void validation_sample(const ValidationView &V, const dropest_validation_opts &opts, dropest_validation_sample &S, std::vector<u32> &a, std::vector<u32> &b);
+	void validation_evaluate(const ValidationView &V, const dropest_validation_opts &opts, dropest_validation_sample &S, const std::vector<u32> &a,
+	                         const std::vector<u32> &b);
+	void run_merge_validation(const dropest_validation_opts *opts, dropest_validation_sample *samples, u32 n_samples);
 	void poisson_build_tables(const u32 *d_counts, u32 n_counts, double total, u32 max_size);
 	void poisson_expected_from_keys(const u32 *d_off, u32 NP, const u64 *d_keys, u32 NK, double *expected_host);
 	// sharded -M (merge_shard.h): this shard's dense UMI histogram; the tables from the summed one; expected sizes of pairs with shipped base rows

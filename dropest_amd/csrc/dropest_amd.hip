@@ -1774,6 +1774,7 @@ void dropest_ctx::sort_filtered(u32 genes_threshold, int max_cells) {
 #include "merge_all.h"
 #include "mutate_host.h"
 #include "matrix_emit.h"
+#include "validation.h"
 
 // ------------------------------------------------------------------------------------------------
 // top-level stages
@@ -1841,6 +1842,7 @@ void dropest_ctx::run_set_initialized() {
 	}
 	request_filtered(0, -1);   // update_cell_sizes(query, 0, -1), CellsDataContainer.cpp:168
 	initialized = true;
+	was_split = false;
 	// cm_raw announced (dropest_set_raw_matrix_prefetch) and nothing in merge_and_filter can change it: its emit and its copy to the
 	// host start now and run under the rest of the pass (the host work of ordering the filtered cells, the emit of cm)
 	if (auto_pf_form >= 0 && n_reads && merge_phase_changes_nothing() && (auto_pf_form != 1 || narrow_possible())) prefetch_raw_matrix(auto_pf_reads, auto_pf_form);
@@ -2686,6 +2688,31 @@ dropest_status dropest_poisson_intersection_prob(dropest_ctx *ctx, uint64_t cell
 		if (intersection_size) *intersection_size = inter;
 		if (expected_intersection_size) *expected_intersection_size = expected;
 		if (merge_probability) *merge_probability = prob;
+	});
+}
+
+dropest_status dropest_merge_validation_samples(dropest_ctx *ctx, const dropest_validation_opts *opts, dropest_validation_sample *samples,
+                                                uint32_t n_samples) {
+	return guarded([&] {
+		if (!ctx) throw InvalidError("null context");
+		ctx->run_merge_validation(opts, samples, n_samples);
+	});
+}
+
+dropest_status dropest_merge_validation(dropest_ctx *ctx, uint32_t min_ed, uint32_t max_ed, uint64_t n_pairs, const dropest_validation_opts *opts,
+                                        uint64_t *cell1, uint64_t *cell2, uint32_t *umis1, uint32_t *umis2, uint32_t *edit_distance,
+                                        uint32_t *intersection, double *expected, double *probability, uint64_t *n_found, uint64_t *draws_used,
+                                        int32_t *complete) {
+	return guarded([&] {
+		if (!ctx) throw InvalidError("null context");
+		dropest_validation_sample S{};
+		S.min_ed = min_ed; S.max_ed = max_ed; S.n_pairs = n_pairs;
+		S.cell1 = cell1; S.cell2 = cell2; S.umis1 = umis1; S.umis2 = umis2; S.edit_distance = edit_distance; S.intersection = intersection;
+		S.expected = expected; S.probability = probability;
+		ctx->run_merge_validation(opts, &S, 1);
+		if (n_found) *n_found = S.n_found;
+		if (draws_used) *draws_used = S.draws_used;
+		if (complete) *complete = S.complete;
 	});
 }
 

@@ -1179,6 +1179,7 @@ void ResultsPrinter::save_mtx(const CellsDataContainer &c, const std::string &ba
 // reads_per_umi_per_cell) is not pinned by anything and is deterministic here: cell-id order, then gene index, then UMI.
 Rds::ValuePtr ResultsPrinter::results_list(const CellsDataContainer &c) const {
 	using namespace Rds;
+	if (validation_stats && c.sharded()) throw std::runtime_error("merge validation statistics (-S) are not built for sharded containers");
 	// DROPEST_RDS_TRACE=1: where save_results spends its time (stderr)
 	const bool rds_trace = getenv("DROPEST_RDS_TRACE") != nullptr;
 	auto rds_t0 = std::chrono::steady_clock::now();
@@ -1360,9 +1361,69 @@ Rds::ValuePtr ResultsPrinter::results_list(const CellsDataContainer &c) const {
 		                                                     {"gene_indexes", integers(std::move(gene_indexes))},
 		                                                     {"reads_per_umi", list(std::move(per_gene))}}));
 	}
+	if (validation_stats) d.emplace_back("merge_validation_info", validation_info(c));   // ResultsPrinter.cpp:66-68
 	lap("chromosome frames and the list");
 	return named_list(std::move(d));
 }
+
+// ResultsPrinter::save_validation_stats (ResultsPrinter.cpp:476-509): one estimator, the distant sample, the adjacent sample.  The
+// std::vector<unsigned> members reach R through Rcpp::wrap, which makes numeric (REALSXP) vectors of them -- unsigned has no integer SEXP
+// type there --: all six entries are written as reals.
+Rds::ValuePtr ResultsPrinter::validation_info(const CellsDataContainer &c) const {
+	using namespace Rds;
+	auto estimator = std::make_shared<Merge::PoissonTargetEstimator>(1, 1);
+	Merge::MergeProbabilityValidator distant(estimator), adjacent(estimator);
+	distant.set_max_draws(validation_max_draws); adjacent.set_max_draws(validation_max_draws);
+	Merge::MergeProbabilityValidator::run_validations(c, {{&distant, 5, 100, validation_distant}, {&adjacent, 1, 1, validation_adjacent}});
+	validation_was_truncated = distant.truncated() || adjacent.truncated();
+	auto sample = [&](const Merge::MergeProbabilityValidator &v) {
+		auto real_of = [](const std::vector<unsigned> &u) { return reals(std::vector<double>(u.begin(), u.end())); };
+		return named_list({{"Probability", reals(v.merge_probs())}, {"UmisPerCell1", real_of(v.umis_per_cell1())}, {"UmisPerCell2", real_of(v.umis_per_cell2())},
+		                   {"EditDistance", real_of(v.edit_distances())}, {"IntersectionSize", real_of(v.intersection_size())},
+		                   {"ExpectedIntersectionSize", reals(v.expected_intersection_size())}});
+	};
+	return list({sample(distant), sample(adjacent)});
+}
+
+namespace Merge {
+void MergeProbabilityValidator::run_validations(const CellsDataContainer &c, const std::vector<Run> &runs) {
+	if (c.sharded()) throw std::runtime_error("merge validation statistics (-S) are not built for sharded containers");
+	if (runs.empty()) return;
+	struct Out { std::vector<uint32_t> u1, u2, ed, inter; std::vector<double> expected, prob; };
+	std::vector<Out> out(runs.size());
+	std::vector<dropest_validation_sample> samples(runs.size());
+	dropest_validation_opts opts{runs[0].validator->_max_draws, 0, 0};
+	for (size_t k = 0; k < runs.size(); ++k) {
+		const size_t n = runs[k].cb_pairs_num;
+		Out &o = out[k];
+		o.u1.resize(n); o.u2.resize(n); o.ed.resize(n); o.inter.resize(n); o.expected.resize(n); o.prob.resize(n);
+		dropest_validation_sample &s = samples[k];
+		s = dropest_validation_sample{};
+		s.min_ed = runs[k].min_ed; s.max_ed = runs[k].max_ed; s.n_pairs = n;
+		s.umis1 = o.u1.data(); s.umis2 = o.u2.data(); s.edit_distance = o.ed.data(); s.intersection = o.inter.data();
+		s.expected = o.expected.data(); s.probability = o.prob.data();
+	}
+	if (dropest_merge_validation_samples(c.handle(), &opts, samples.data(), uint32_t(samples.size())) != DROPEST_OK) throw std::runtime_error(dropest_last_error());
+	for (size_t k = 0; k < runs.size(); ++k) {
+		MergeProbabilityValidator &v = *runs[k].validator;
+		const size_t n = size_t(samples[k].n_found);
+		const Out &o = out[k];
+		v._umis_per_cell1.insert(v._umis_per_cell1.end(), o.u1.begin(), o.u1.begin() + n);
+		v._umis_per_cell2.insert(v._umis_per_cell2.end(), o.u2.begin(), o.u2.begin() + n);
+		v._edit_distances.insert(v._edit_distances.end(), o.ed.begin(), o.ed.begin() + n);
+		v._intersection_size.insert(v._intersection_size.end(), o.inter.begin(), o.inter.begin() + n);
+		v._merge_probs.insert(v._merge_probs.end(), o.prob.begin(), o.prob.begin() + n);
+		v._expected_intersection_size.insert(v._expected_intersection_size.end(), o.expected.begin(), o.expected.begin() + n);
+		v._truncated = !samples[k].complete;
+		v._draws_used = samples[k].draws_used;
+	}
+}
+
+void MergeProbabilityValidator::run_validation(const CellsDataContainer &container, unsigned min_ed, unsigned max_ed, size_t cb_pairs_num, unsigned) {
+	if (container.filtered_cells().empty()) return;                     // MergeProbabilityValidator.cpp:11-12
+	run_validations(container, {{this, min_ed, max_ed, cb_pairs_num}});
+}
+}  // namespace Merge
 
 // Rds::Compressor over include/dropest_deflate.h: the pieces of a batch side by side in the handle's pinned buffer, one launch, the stream back
 // as the batch's first entry.  Any device error: this batch (and, when the handle could not be made, every batch) through zlib on the host.

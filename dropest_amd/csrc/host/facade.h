@@ -523,16 +523,65 @@ public:
 	std::string decode(uint64_t code) const;
 };
 
+namespace Merge {
+// Estimation/Merge/MergeProbabilityValidator.h (`dropest -S`): random pairs of filtered cells whose barcodes are min_ed .. max_ed apart and the
+// estimator's numbers for each, over dropest_merge_validation_samples.  Every run_validation restarts the rand() sequence at srand(42)
+// (MergeProbabilityValidator.cpp:14) and appends to the vectors, like the reference.  The reference does not return when no pair qualifies;
+// here a run tests at most max_draws() candidate pairs (0: the library's default, 2^30) and truncated() says whether the last run stopped
+// there with fewer pairs.  run_validations: several runs over ONE view of the molecules and one set of estimator tables -- one validator per
+// run -- as save_validation_stats uses one estimator for both of its samples (ResultsPrinter.cpp:476-509).  Not on a sharded container.
+class MergeProbabilityValidator {
+public:
+	using u_vec_t = std::vector<unsigned>;
+	using d_vec_t = std::vector<double>;
+	struct Run { MergeProbabilityValidator *validator; unsigned min_ed, max_ed; size_t cb_pairs_num; };
+private:
+	u_vec_t _umis_per_cell1, _umis_per_cell2, _edit_distances, _intersection_size;
+	d_vec_t _merge_probs, _expected_intersection_size;
+	std::shared_ptr<PoissonTargetEstimator> _estimator;
+	uint64_t _max_draws = 0, _draws_used = 0;
+	bool _truncated = false;
+public:
+	explicit MergeProbabilityValidator(const std::shared_ptr<PoissonTargetEstimator> &estimator) : _estimator(estimator) {}
+	void run_validation(const CellsDataContainer &container, unsigned min_ed, unsigned max_ed, size_t cb_pairs_num, unsigned log_period = 0);
+	static void run_validations(const CellsDataContainer &container, const std::vector<Run> &runs);
+	void set_max_draws(uint64_t max_draws) { _max_draws = max_draws; }
+	uint64_t max_draws() const { return _max_draws; }
+	bool truncated() const { return _truncated; }
+	uint64_t draws_used() const { return _draws_used; }
+	const u_vec_t &umis_per_cell1() const { return _umis_per_cell1; }
+	const u_vec_t &umis_per_cell2() const { return _umis_per_cell2; }
+	const u_vec_t &edit_distances() const { return _edit_distances; }
+	const d_vec_t &merge_probs() const { return _merge_probs; }
+	const u_vec_t &intersection_size() const { return _intersection_size; }
+	const d_vec_t &expected_intersection_size() const { return _expected_intersection_size; }
+};
+}  // namespace Merge
+
 // Count-matrix assembly and the MatrixMarket writer of ResultsPrinter (Estimation/ResultsPrinter.cpp:334-396, :81-91).
 class ResultsPrinter {
-	const bool write_matrix, reads_output, umi_correction_info;
+	const bool write_matrix, reads_output, validation_stats, umi_correction_info;
 public:
 	struct SparseMatrix {            // dgCMatrix layout (CSC), rows = genes, columns = cells
 		std::vector<std::string> row_names, col_names;
 		std::vector<uint32_t> colptr, rowidx, values;
 	};
-	ResultsPrinter(bool write_matrix_, bool reads_output_, bool /*validation_stats*/ = false, bool umi_correction_info_ = false)
-		: write_matrix(write_matrix_), reads_output(reads_output_), umi_correction_info(umi_correction_info_) {}
+	ResultsPrinter(bool write_matrix_, bool reads_output_, bool validation_stats_ = false, bool umi_correction_info_ = false)
+		: write_matrix(write_matrix_), reads_output(reads_output_), validation_stats(validation_stats_), umi_correction_info(umi_correction_info_) {}
+	// -S (validation_stats): d$merge_validation_info = list(distant, adjacent) after reads_per_umi_per_cell (ResultsPrinter.cpp:66-68, :476-509):
+	// 1 000 000 pairs at 5 .. 100 and 100 000 at exactly 1.  max_draws caps the candidate pairs a sample tests (0: the library's default; the
+	// reference has no cap and does not return when too few pairs qualify); a sample that stopped there is written with the pairs it found and
+	// validation_truncated() says so after save_results / results_list.  The sizes are the reference's unless set otherwise (tests).  A sharded
+	// container with validation_stats throws before anything is written.
+	void set_validation_max_draws(uint64_t max_draws) { validation_max_draws = max_draws; }
+	void set_validation_sizes(size_t distant_pairs, size_t adjacent_pairs) { validation_distant = distant_pairs; validation_adjacent = adjacent_pairs; }
+	bool validation_truncated() const { return validation_was_truncated; }
+private:
+	uint64_t validation_max_draws = 0;
+	size_t validation_distant = 1000000, validation_adjacent = 100000;
+	mutable bool validation_was_truncated = false;
+	std::shared_ptr<Rds::Value> validation_info(const CellsDataContainer &container) const;
+public:
 	// get_count_matrix / save_mtx / save_results name the matrix straight from the byte form that crossed PCIe (two bytes per entry, decoded
 	// column by column on the calling thread) instead of from the 32-bit slots; false takes the slots (dropest_count_matrix_csc)
 	bool walk_byte_form = true;
@@ -566,7 +615,7 @@ public:
 	// <base>.mtx + <base>.cells.tsv + <base>.genes.tsv (what save_mtx writes through R's Matrix::writeMM)
 	void save_mtx(const CellsDataContainer &container, const std::string &filename_base) const;
 	// <base>.rds: the R list d = list(cm, cm_raw, reads_per_chr_per_cells, mean_reads_per_umi, saturation_info, merge_targets,
-	// aligned_reads_per_cell, aligned_umis_per_cell, requested_umis_per_cb, requested_reads_per_cb[, reads_per_umi_per_cell]),
+	// aligned_reads_per_cell, aligned_umis_per_cell, requested_umis_per_cb, requested_reads_per_cb[, reads_per_umi_per_cell][, merge_validation_info]),
 	// written natively in R's serialisation format (rds_writer.h); + the matrix triple with write_matrix
 	void save_results(const CellsDataContainer &container, const std::string &filename) const;
 	// The .rds files' DEFLATE on the device (include/dropest_deflate.h) instead of zlib level 4 on host threads: host threads materialise a

@@ -370,22 +370,25 @@ void dropest_ctx::poisson_expected_from_keys(const u32 *d_off, u32 NP, const u64
 	fetch(expected_host, d_expected.p, size_t(NP) * 8);
 }
 
-// Expected intersection sizes of S's pairs on the current device state (single context).
-std::vector<double> dropest_ctx::poisson_expected_intersections(const std::vector<u32> &pair_base_cell, const std::vector<u32> &pair_cand_cell) {
+// The estimator's tables from the UMI distribution of the filtered cells on the current device state (steps 1 and 2 of
+// poisson_expected_intersections; ptab.ready says whether there is anything to estimate with).
+void dropest_ctx::poisson_tables_from_state() {
 	using namespace dropest;
-	const u32 NP = u32(pair_base_cell.size());
-	std::vector<double> expected(NP, 0.0);
-	if (!NP) return expected;
 	const KeyLayout &L = layout;
-	const u64 gene_mask = L.gene_none;
-
+	ptab = PoissonTables{};
 	// 1. UMI distribution of the filtered cells: sorted codes -> one count per distinct UMI
 	u32 kept = 0, max_size = 0;
 	poisson_local_umis(kept, max_size);
-	if (!kept || !max_size) return expected;
+	if (!kept || !max_size) return;
+	poisson_tables_from_umi_codes(kept, L.umi_bits >= 64 ? ~0ull : ((1ull << L.umi_bits) - 1ull), max_size);
+}
+
+// keys_a[0 .. kept) hold one UMI code per molecule (any order): runs of equal codes -> counts -> tables
+void dropest_ctx::poisson_tables_from_umi_codes(u32 kept, u64 code_mask, u32 max_size) {
+	using namespace dropest;
 	u64 *k = keys_a.p, *k_alt = keys_b.p;
 	u32 *v = vals_a.p, *v_alt = vals_b.p;
-	radix_sort(k, v, k_alt, v_alt, kept, L.umi_bits >= 64 ? ~0ull : ((1ull << L.umi_bits) - 1ull));
+	radix_sort(k, v, k_alt, v_alt, kept, code_mask);
 	UmiRuns runs_policy{};
 	runs_policy.keys = k;
 	DevBuf<u64> run_key; DevBuf<u32> run_cnt;
@@ -396,32 +399,56 @@ std::vector<double> dropest_ctx::poisson_expected_intersections(const std::vecto
 	});
 	// 2. classes of equally frequent UMIs, adjusted sizes 1..max_size (Tools::CollisionsAdjuster)
 	poisson_build_tables(run_cnt.p, n_umis, double(kept), max_size);
-	if (!ptab.ready) return expected;
+}
 
+// expected[p] of the pairs (d_pb[p], d_pc[p]) over the (cell, gene) tables of `src` with the tables in ptab (steps 3 and 4).  count_host:
+// the pairs' numbers of common genes when the caller has them already (common_genes_kernel<false>), else null.
+void dropest_ctx::poisson_expected_pairs(const PoissonSource &src, const u32 *d_pb, const u32 *d_pc, u32 NP, const u32 *count_host, double *expected) {
+	using namespace dropest;
+	for (u32 p = 0; p < NP; ++p) expected[p] = 0.0;
+	if (!NP) return;
 	// 3. genes in common of every pair -> keys of adjusted sizes
-	DevBuf<u32> d_pb, d_pc, d_cnt, d_off;
-	d_pb.alloc(NP); d_pc.alloc(NP); d_cnt.alloc(NP); d_off.alloc(size_t(NP) + 1);
-	HIP_CHECK(hipMemcpyAsync(d_pb.p, pair_base_cell.data(), size_t(NP) * 4, hipMemcpyHostToDevice, stream));
-	HIP_CHECK(hipMemcpyAsync(d_pc.p, pair_cand_cell.data(), size_t(NP) * 4, hipMemcpyHostToDevice, stream));
-	hipLaunchKernelGGL(common_genes_kernel<false>, dim3(div_up(NP, 256)), dim3(256), 0, stream, d_pb.p, d_pc.p, NP, cell_cg_begin.p,
-	                   cell_cg_count.p, cg_key.p, cg_mol_begin.p, gene_mask, ptab.adj.p, d_cnt.p, nullptr, nullptr);
-	HIP_CHECK(hipGetLastError());
-	std::vector<u32> cnt(NP), off(size_t(NP) + 1, 0);
-	fetch(cnt.data(), d_cnt.p, size_t(NP) * 4);
+	DevBuf<u32> d_cnt, d_off;
+	d_cnt.alloc(NP); d_off.alloc(size_t(NP) + 1);
+	std::vector<u32> cnt_own, off(size_t(NP) + 1, 0);
+	if (!count_host) {
+		hipLaunchKernelGGL(common_genes_kernel<false>, dim3(div_up(NP, 256)), dim3(256), 0, stream, d_pb, d_pc, NP, src.cell_cg_begin,
+		                   src.cell_cg_count, src.cg_key, src.cg_mol_begin, src.gene_mask, ptab.adj.p, d_cnt.p, nullptr, nullptr);
+		HIP_CHECK(hipGetLastError());
+		cnt_own.resize(NP);
+		fetch(cnt_own.data(), d_cnt.p, size_t(NP) * 4);
+		count_host = cnt_own.data();
+	}
 	u64 total = 0;
-	for (u32 p = 0; p < NP; ++p) { off[p] = u32(total); total += cnt[p]; }
+	for (u32 p = 0; p < NP; ++p) { off[p] = u32(total); total += count_host[p]; }
 	if (total >= 0xFFFFFFFFull) throw UnsupportedError("too many common genes over the merge candidates");
 	off[NP] = u32(total);
-	if (!total) return expected;
+	if (!total) return;
 	const u32 NK = u32(total);
 	HIP_CHECK(hipMemcpyAsync(d_off.p, off.data(), (size_t(NP) + 1) * 4, hipMemcpyHostToDevice, stream));
 	DevBuf<u64> d_keys; d_keys.alloc(NK);
-	hipLaunchKernelGGL(common_genes_kernel<true>, dim3(div_up(NP, 256)), dim3(256), 0, stream, d_pb.p, d_pc.p, NP, cell_cg_begin.p,
-	                   cell_cg_count.p, cg_key.p, cg_mol_begin.p, gene_mask, ptab.adj.p, d_cnt.p, d_off.p, d_keys.p);
+	hipLaunchKernelGGL(common_genes_kernel<true>, dim3(div_up(NP, 256)), dim3(256), 0, stream, d_pb, d_pc, NP, src.cell_cg_begin,
+	                   src.cell_cg_count, src.cg_key, src.cg_mol_begin, src.gene_mask, ptab.adj.p, d_cnt.p, d_off.p, d_keys.p);
 	HIP_CHECK(hipGetLastError());
 
 	// 4. one est() per distinct key, summed per pair
-	poisson_expected_from_keys(d_off.p, NP, d_keys.p, NK, expected.data());
+	poisson_expected_from_keys(d_off.p, NP, d_keys.p, NK, expected);
+}
+
+// Expected intersection sizes of S's pairs on the current device state (single context).
+std::vector<double> dropest_ctx::poisson_expected_intersections(const std::vector<u32> &pair_base_cell, const std::vector<u32> &pair_cand_cell) {
+	using namespace dropest;
+	const u32 NP = u32(pair_base_cell.size());
+	std::vector<double> expected(NP, 0.0);
+	if (!NP) return expected;
+	poisson_tables_from_state();
+	if (!ptab.ready) return expected;
+	DevBuf<u32> d_pb, d_pc;
+	d_pb.alloc(NP); d_pc.alloc(NP);
+	HIP_CHECK(hipMemcpyAsync(d_pb.p, pair_base_cell.data(), size_t(NP) * 4, hipMemcpyHostToDevice, stream));
+	HIP_CHECK(hipMemcpyAsync(d_pc.p, pair_cand_cell.data(), size_t(NP) * 4, hipMemcpyHostToDevice, stream));
+	const PoissonSource src{cell_cg_begin.p, cell_cg_count.p, cg_key.p, cg_mol_begin.p, layout.gene_none};
+	poisson_expected_pairs(src, d_pb.p, d_pc.p, NP, nullptr, expected.data());
 	return expected;
 }
 

@@ -2398,6 +2398,7 @@ static dropest_shard *make_shard(const dropest_cfg *cfg, int rank, int world) {
 	std::unique_ptr<dropest_shard> s(new dropest_shard());
 	s->ctx.reset(new dropest_ctx());
 	s->ctx->init_from_cfg(*cfg);
+	s->ctx->is_shard_ctx = true;
 	s->rank = rank; s->world = world;
 	if (const char *e = getenv("DROPEST_SHARD_TRACE")) s->trace = atoi(e) != 0;
 	if (const char *e = getenv("DROPEST_SHARD_FORCE_EXCHANGE")) s->force_exchange = atoi(e) != 0;
@@ -2469,6 +2470,7 @@ dropest_status dropest_ctx_split(dropest_ctx *ctx, int32_t parts, dropest_shard 
 		ctx->concat_chunks();
 		ctx->free_results();
 		ctx->release_tables();   // the shards need the room; the reads stay
+		ctx->was_split = true;
 		auto hub = std::make_shared<dropest::LocalHub>(parts);
 		std::vector<std::unique_ptr<dropest_shard>> made;
 		const uint64_t n = ctx->n_reads;

@@ -353,6 +353,55 @@ dropest_status dropest_poisson_upper_tail(int64_t k, double lambda, double *out)
  * P(Poisson(expected) >= intersection).  expected = -1 and probability = 1 when the intersection is empty (:72-75). */
 dropest_status dropest_poisson_intersection_prob(dropest_ctx *ctx, uint64_t cell1, uint64_t cell2, uint64_t *intersection_size,
                                                  double *expected_intersection_size, double *merge_probability);
+/* ---- merge validation statistics: `dropest -S` (dropest.cpp:127,188,312; ResultsPrinter.cpp:66-68, :476-509) ----
+ * MergeProbabilityValidator::run_validation (Estimation/Merge/MergeProbabilityValidator.cpp:8-46): random pairs of filtered cells
+ * whose barcodes are min_ed..max_ed apart, and for each the estimator's intersection size, expected size and probability on the
+ * CURRENT state of the container (after merge_and_filter: the merged one, as save_validation_stats sees it).
+ *
+ * Every sample restarts rand() at srand(42) (:14) -- a generator local to the call, neither the process's nor the container's -- and
+ * every candidate takes two values: cell1 = filtered[rand() % F], cell2 = filtered[rand() % F] (:27-28).  cell1 == cell2 is rejected
+ * (:29-30); otherwise ed = Tools::edit_distance(barcode1, barcode2, true, min_ed) (:32; Tools/UtilFunctions.cpp:32-65: 'N' matches
+ * anything, the band is min_ed, the function returns early with a row's minimum once that exceeds the band) and the pair is accepted
+ * when min_ed <= ed <= max_ed (:33).  The recorded distance is that function's value, not a Levenshtein distance.
+ *
+ * The reference loops for ever when no pair qualifies.  Here a sample tests at most max_draws candidate pairs (default 2^30: a policy,
+ * the reference has none) and reports what it found: n_found, draws_used (candidates tested up to and including the last recorded
+ * pair of a complete sample; all that were tested otherwise) and complete.  F < 2 returns at once with nothing found.
+ *
+ * The sampler runs on the device in rounds of candidates (round_candidates; default: a little over n_pairs first, then scaled by the
+ * acceptance rate seen so far).  The pairs are evaluated in chunks of at most max_keys_per_chunk common genes (default: from the free
+ * device memory; a pair above it goes alone).  Neither changes any output.  Zero in an option means its default.
+ *
+ * Outputs, sized for n_pairs by the caller, entries [0, n_found): cell ids (not part of the reference's record), umis_number() of
+ * both cells (:39-40), ed (:41), intersection size, expected size and probability (:42-44; -1 and 1 for an empty intersection).
+ * Any output pointer may be null.  Needs an initialised context, before or after merge_and_filter; a shard's context and a context
+ * that dropest_ctx_split emptied are refused (UNSUPPORTED).
+ * dropest_merge_validation_samples: several samples over one view of the molecules and one set of estimator tables, as
+ * save_validation_stats runs its two over one estimator (ResultsPrinter.cpp:476-509). */
+typedef struct dropest_validation_opts {
+	uint64_t max_draws;            /* candidate pairs tested per sample at most */
+	uint64_t round_candidates;     /* candidates per sampler round */
+	uint64_t max_keys_per_chunk;   /* common genes materialised at a time */
+} dropest_validation_opts;
+typedef struct dropest_validation_sample {
+	uint32_t min_ed, max_ed;       /* in */
+	uint64_t n_pairs;              /* in */
+	uint64_t *cell1, *cell2;       /* out arrays, any may be null */
+	uint32_t *umis1, *umis2, *edit_distance, *intersection;
+	double *expected, *probability;
+	uint64_t n_found, draws_used;  /* out */
+	int32_t complete;              /* out: n_found == n_pairs */
+	uint32_t rounds, chunks;       /* out: sampler rounds, evaluation chunks */
+	uint32_t reserved;
+	double ms_view, ms_sampler, ms_evaluation;   /* out: wall time of the steps (the view is built once for all samples) */
+} dropest_validation_sample;
+dropest_status dropest_merge_validation(dropest_ctx *ctx, uint32_t min_ed, uint32_t max_ed, uint64_t n_pairs,
+                                        const dropest_validation_opts *opts, uint64_t *cell1, uint64_t *cell2, uint32_t *umis1,
+                                        uint32_t *umis2, uint32_t *edit_distance, uint32_t *intersection, double *expected,
+                                        double *probability, uint64_t *n_found, uint64_t *draws_used, int32_t *complete);
+dropest_status dropest_merge_validation_samples(dropest_ctx *ctx, const dropest_validation_opts *opts,
+                                                dropest_validation_sample *samples, uint32_t n_samples);
+
 /* RealBarcodesMergeStrategy::get_merge_target (RealBarcodesMergeStrategy.cpp:22-29) for one cell,
  * evaluated on the un-merged state; valid between set_initialized and merge_and_filter. */
 dropest_status dropest_merge_target(dropest_ctx *ctx, uint64_t cell, int64_t *target);
