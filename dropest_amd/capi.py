@@ -224,6 +224,7 @@ def lib():
         "dropest_shard_merged_barcodes": (C.c_int, [vp, u64p, vp, vp]),
         "dropest_shard_phase_stats": (C.c_int, [vp, P(C.c_uint32), vp]),
         "dropest_shard_set_option": (C.c_int, [vp, C.c_char_p, C.c_int64]),
+        "dropest_test_transport": (C.c_int, [C.c_int, C.c_int32, C.c_int32, vp, C.c_int, C.c_uint32]),
         "dropest_key_width": (C.c_int, [vp, P(C.c_uint32), P(C.c_uint32), P(C.c_uint32)]),
         "dropest_ctx_split": (C.c_int, [vp, C.c_int32, vp]),
         "dropest_plan_columns": (C.c_int, [C.c_uint64, vp, vp, vp, vp, vp, vp, C.c_int, C.c_uint32, C.c_int32, vp, C.c_uint64, u64p, vp]),
@@ -258,7 +259,7 @@ EXPORTED_SYMBOLS = [
     "dropest_rand_sequence", "dropest_table_sizes",
     "dropest_shard_unique_id", "dropest_shard_create", "dropest_shard_group_create", "dropest_shard_destroy", "dropest_shard_ctx",
     "dropest_shard_set_reads_device", "dropest_shard_push_reads", "dropest_shard_push_reads_device", "dropest_deal_range", "dropest_reserve_reads", "dropest_shard_step", "dropest_shard_group_step", "dropest_shard_matrix", "dropest_shard_matrix_form",
-    "dropest_shard_merged_barcodes", "dropest_shard_phase_stats", "dropest_shard_set_option", "dropest_plan_columns",
+    "dropest_shard_merged_barcodes", "dropest_shard_phase_stats", "dropest_shard_set_option", "dropest_test_transport", "dropest_plan_columns",
     "dropest_key_width", "dropest_ctx_split", "dropest_shard_matrix_narrow", "dropest_shard_matrix_bytes", "dropest_add_umi_to_cell", "dropest_umi_first_seen", "dropest_resident_reads", "dropest_prefetch_raw_matrix_narrow", "dropest_narrow_matrix_possible", "dropest_count_matrix_csc_narrow",
     "dropest_prefetch_raw_matrix_bytes", "dropest_count_matrix_csc_bytes", "dropest_matrix_bytes_widen", "dropest_matrix_rider_widen", "dropest_set_raw_matrix_prefetch", "dropest_set_matrix_wire", "dropest_set_umi_dictionary", "dropest_debug_refresh", "dropest_push_reads_gather", "dropest_shard_set_umi_qualities", "dropest_shard_set_umi_qualities_var",
     "dropest_debug_poison_scratch", "dropest_debug_trim_pool", "dropest_debug_alloc_ordinal", "dropest_debug_alloc_site",

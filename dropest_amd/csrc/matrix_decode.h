@@ -49,7 +49,7 @@ struct ByteMatrixView {
 	const uint8_t *rd = nullptr, *vb = nullptr;   // row deltas, values
 	const uint32_t *colptr = nullptr;             // column c = entries [colptr[c], colend ? colend[c] : colptr[c + 1])
 	const uint32_t *colend = nullptr;             // set: the columns are a SELECTION of a larger matrix's (one shard's columns of the global
-	                                              // matrix of a sharded run, csrc/shard_run.h), each with its own begin and end
+	                                              // matrix of a sharded run, csrc/shard_matrix.h), each with its own begin and end
 	const uint32_t *bytebeg = nullptr;            // set (with colend): the bytes of column c stand at [bytebeg[c], ...) of rd / vb -- a shard's LOCAL byte
 	                                              // arrays, contiguous in its own column order -- while colptr / colend name the column's place in ro / vo
 	uint64_t ncols = 0, nnz = 0;

@@ -5,838 +5,19 @@
 // (SURVEY.md §8e).  One ShardRun = one shard = one dropest_ctx on one GPU, driven by one host thread -- a process per GPU
 // (bench.py under torch.distributed.run: the communicator comes from an ncclUniqueId the launcher distributes) or the
 // threads of one process (the C++ facade owning N GPUs; tests put several shards on ONE device).  Everything between the
-// collectives is the single-GPU pipeline; the collectives go through a Transport:
-//   RcclTransport   RCCL over xGMI: one grouped ncclSend / ncclRecv all-to-all(v) of the five read arrays (the only
+// collectives is the single-GPU pipeline; the collectives go through a Transport (transport.h):
+//   RcclTransport   RCCL over xGMI: one grouped ncclSend / ncclRecv all-to-all(v) of the read records (the only
 //                   data-path collective), all-gathers of small tables, molecule rows of merged cells
 //   LocalTransport  shards inside one process: device-to-device copies and a host barrier (several shards per device)
-// Steps of one pass: partition by owner (stable) -> all-to-all -> barcode table + key-field agreement -> sort / reduce ->
-// whitelist CB merge across shards (search / export / intersect / decide / apply / finish, merge_shard.h) -> UMI merge
-// (N-UMIs: random fills follow ONE rand() sequence in global cell order) and filter -> global column order -> every
-// shard writes ITS columns of both matrices into host memory shared by the node's shards (all PCIe links at once).
+// Steps of one pass (dropest_shard::step): partition by owner (stable) -> all-to-all -> barcode table + key-field agreement ->
+// sort / reduce -> whitelist CB merge across shards (search / export / intersect / decide / apply / finish, merge_shard.h;
+// without a whitelist: shard_merge_free.h) -> UMI merge (N-UMIs: random fills follow ONE rand() sequence in global cell order)
+// and filter -> global column order -> every shard writes ITS columns of both matrices into host memory shared by the node's
+// shards (all PCIe links at once; shard_matrix.h).  The small kernels are in k_shard.h, the transports' test hooks in transport_test.h.
 #pragma once
 
-#include <rccl/rccl.h>
-
-#include <atomic>
-#include <chrono>
-#include <condition_variable>
-#include <sched.h>
-#include <sys/stat.h>
-#include <dlfcn.h>
-#include <fcntl.h>
-#include <mutex>
-#include <sys/mman.h>
-#include <unistd.h>
-
-namespace dropest {
-
-// ---- RCCL, bound at run time (the library also works on hosts without it: single-GPU use never touches it) -----------
-struct RcclApi {
-	void *handle = nullptr;
-	ncclResult_t (*GetUniqueId)(ncclUniqueId *) = nullptr;
-	ncclResult_t (*CommInitRank)(ncclComm_t *, int, ncclUniqueId, int) = nullptr;
-	ncclResult_t (*CommDestroy)(ncclComm_t) = nullptr;
-	ncclResult_t (*GroupStart)() = nullptr;
-	ncclResult_t (*GroupEnd)() = nullptr;
-	ncclResult_t (*Send)(const void *, size_t, ncclDataType_t, int, ncclComm_t, hipStream_t) = nullptr;
-	ncclResult_t (*Recv)(void *, size_t, ncclDataType_t, int, ncclComm_t, hipStream_t) = nullptr;
-	ncclResult_t (*AllGather)(const void *, void *, size_t, ncclDataType_t, ncclComm_t, hipStream_t) = nullptr;
-	const char *(*GetErrorString)(ncclResult_t) = nullptr;
-	static RcclApi &get() {
-		static RcclApi api = [] {
-			RcclApi a;
-			// The RCCL that belongs to the HIP runtime this library runs on: a process may hold two ROCm trees (PyTorch ships its
-			// own next to /opt/rocm), and an RCCL from the other tree opens ITS libhsa-runtime64 -- not initialised -- and fails
-			// with "no ROCm-capable device".  So: the directory libamdhip64 was loaded from first, then the default search.
-			Dl_info hip{};
-			if (dladdr(reinterpret_cast<void *>(&hipGetDeviceCount), &hip) && hip.dli_fname) {
-				std::string dir(hip.dli_fname);
-				const size_t slash = dir.rfind('/');
-				if (slash != std::string::npos) {
-					dir.resize(slash + 1);
-					for (const char *name : {"librccl.so.1", "librccl.so"}) if ((a.handle = dlopen((dir + name).c_str(), RTLD_NOW | RTLD_GLOBAL))) break;
-				}
-			}
-			if (!a.handle) for (const char *name : {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"}) if ((a.handle = dlopen(name, RTLD_NOW | RTLD_GLOBAL))) break;
-			if (!a.handle) return a;
-			auto sym = [&](const char *n) { return dlsym(a.handle, n); };
-			a.GetUniqueId = reinterpret_cast<decltype(a.GetUniqueId)>(sym("ncclGetUniqueId"));
-			a.CommInitRank = reinterpret_cast<decltype(a.CommInitRank)>(sym("ncclCommInitRank"));
-			a.CommDestroy = reinterpret_cast<decltype(a.CommDestroy)>(sym("ncclCommDestroy"));
-			a.GroupStart = reinterpret_cast<decltype(a.GroupStart)>(sym("ncclGroupStart"));
-			a.GroupEnd = reinterpret_cast<decltype(a.GroupEnd)>(sym("ncclGroupEnd"));
-			a.Send = reinterpret_cast<decltype(a.Send)>(sym("ncclSend"));
-			a.Recv = reinterpret_cast<decltype(a.Recv)>(sym("ncclRecv"));
-			a.AllGather = reinterpret_cast<decltype(a.AllGather)>(sym("ncclAllGather"));
-			a.GetErrorString = reinterpret_cast<decltype(a.GetErrorString)>(sym("ncclGetErrorString"));
-			if (!a.GetUniqueId || !a.CommInitRank || !a.CommDestroy || !a.GroupStart || !a.GroupEnd || !a.Send || !a.Recv || !a.AllGather) a.handle = nullptr;
-			return a;
-		}();
-		if (!api.handle) throw DeviceError("RCCL (librccl.so) is not available: sharded runs over several GPUs need it");
-		return api;
-	}
-	void check(ncclResult_t r, const char *what) const {
-		if (r != ncclSuccess) throw DeviceError(std::string("RCCL ") + what + ": " + (GetErrorString ? GetErrorString(r) : "error"));
-	}
-};
-
-// ---- transports --------------------------------------------------------------------------------------------------------
-struct Transport {
-	int rank = 0, world = 1;
-	virtual ~Transport() {}
-	virtual const char *name() const = 0;
-	// all-to-all(v) of n_arrays device arrays at once: array a has elem[a]-byte elements; the block for peer p starts at
-	// element sum(send_cnt[< p]) of d_send[a] and lands at element sum(recv_cnt[< p]) of d_recv[a].  Returns when done.
-	// in_place: bit a set = the block of array a that stays on this shard is NOT copied (the caller reads it in d_send[a])
-	virtual void exchange(int n_arrays, const void *const *d_send, void *const *d_recv, const size_t *elem, const uint64_t *send_cnt,
-	                      const uint64_t *recv_cnt, hipStream_t st, uint32_t in_place = 0) = 0;
-	// One chunk of such an all-to-all(v): the piece for peer p starts at element send_off[p] of d_send[a] (send_cnt[p] elements) and lands at
-	// element recv_off[p] of d_recv[a] (recv_cnt[p] elements).  Enqueued on `st` and NOT waited for where the transport can (RCCL): the
-	// caller orders its consumers with an event on `st` -- the next chunk is partitioned, the previous one hashed, while this one travels.
-	virtual void exchange_at(int n_arrays, const void *const *d_send, void *const *d_recv, const size_t *elem, const uint64_t *send_off, const uint64_t *send_cnt,
-	                         const uint64_t *recv_off, const uint64_t *recv_cnt, hipStream_t st, uint32_t in_place = 0) = 0;
-	virtual void gather_host(const void *mine, size_t bytes, void *all) = 0;   // all: world x bytes, rank order
-	// every shard's device block to every shard: block of rank p = bytes[p] at d_all + off[p]
-	virtual void gather_dev(const void *d_mine, void *d_all, const size_t *off, const size_t *bytes, hipStream_t st) = 0;
-	virtual void barrier() = 0;
-	// host memory shared by the shards of the node (collective call; at least `bytes`); *d_ptr = this shard's device view
-	virtual void *shared_host(int slot, size_t bytes, void **d_ptr) = 0;
-
-	template <class T>
-	void gather_vec(const std::vector<T> &mine, std::vector<T> &all, std::vector<size_t> &count) {   // variable-length host rows
-		// ONE collective when every rank's rows fit a small fixed slot (the length travels in front of them) -- most of a pass's
-		// host gathers are a few hundred bytes, and a collective of staged bytes costs its latency, not its size; a second one
-		// with the padded rows only when somebody's did not fit.
-		constexpr size_t SLOT = 16384;
-		const uint64_t n = mine.size();
-		const size_t fit = (SLOT - 8) / sizeof(T);
-		std::vector<unsigned char> slot(SLOT, 0), slots(SLOT * size_t(world));
-		std::memcpy(slot.data(), &n, 8);
-		if (n && n <= fit) std::memcpy(slot.data() + 8, mine.data(), size_t(n) * sizeof(T));
-		gather_host(slot.data(), SLOT, slots.data());
-		std::vector<uint64_t> ns(size_t(world), 0);
-		uint64_t mx = 0;
-		for (int p = 0; p < world; ++p) { std::memcpy(&ns[size_t(p)], slots.data() + size_t(p) * SLOT, 8); mx = std::max(mx, ns[size_t(p)]); }
-		count.assign(size_t(world), 0);
-		all.clear();
-		if (mx <= fit) {
-			for (int p = 0; p < world; ++p) {
-				count[size_t(p)] = size_t(ns[size_t(p)]);
-				const T *rows = reinterpret_cast<const T *>(slots.data() + size_t(p) * SLOT + 8);
-				all.insert(all.end(), rows, rows + ns[size_t(p)]);
-			}
-			return;
-		}
-		std::vector<T> pad(mx), buf(size_t(mx) * size_t(world));
-		if (n) std::memcpy(static_cast<void *>(pad.data()), mine.data(), size_t(n) * sizeof(T));
-		gather_host(pad.data(), size_t(mx) * sizeof(T), buf.data());
-		for (int p = 0; p < world; ++p) {
-			count[size_t(p)] = size_t(ns[size_t(p)]);
-			all.insert(all.end(), buf.begin() + size_t(p) * mx, buf.begin() + size_t(p) * mx + ns[size_t(p)]);
-		}
-	}
-};
-
-// Shards inside one process.  One hub per group; every member runs on its own host thread.
-struct LocalHub {
-	int n;
-	std::mutex m;
-	std::condition_variable cv;
-	int arrived = 0;
-	uint64_t generation = 0;
-	std::vector<const void *> p0, p1;   // per rank: pointers published for the current collective
-	struct Shared { void *host = nullptr; size_t bytes = 0; } shared[4];
-	bool failed = false;                // a member threw: wake the others instead of deadlocking
-	explicit LocalHub(int n_) : n(n_), p0(size_t(n_), nullptr), p1(size_t(n_), nullptr) {}
-	~LocalHub() { for (auto &s : shared) if (s.host) (void)hipHostFree(s.host); }
-	void barrier() {
-		std::unique_lock<std::mutex> lk(m);
-		if (failed) throw DeviceError("another shard of the group failed");
-		const uint64_t g = generation;
-		if (++arrived == n) { arrived = 0; ++generation; cv.notify_all(); return; }
-		cv.wait(lk, [&] { return generation != g || failed; });
-		if (failed && generation == g) throw DeviceError("another shard of the group failed");
-	}
-	void fail() { std::lock_guard<std::mutex> lk(m); failed = true; cv.notify_all(); }
-};
-
-struct LocalTransport : Transport {
-	std::shared_ptr<LocalHub> hub;
-	LocalTransport(std::shared_ptr<LocalHub> h, int r) : hub(std::move(h)) { rank = r; world = hub->n; }
-	const char *name() const override { return "local"; }
-	struct Pub { const void *const *d_send; const size_t *elem; const uint64_t *send_cnt; };
-	void exchange(int n_arrays, const void *const *d_send, void *const *d_recv, const size_t *elem, const uint64_t *send_cnt,
-	              const uint64_t *recv_cnt, hipStream_t st, uint32_t in_place = 0) override {
-		HIP_CHECK(stream_wait(st));   // the blocks the peers copy were written on this stream
-		Pub pub{d_send, elem, send_cnt};
-		hub->p0[size_t(rank)] = &pub;
-		hub->barrier();
-		uint64_t roff = 0;
-		for (int p = 0; p < world; ++p) {
-			const Pub *src = static_cast<const Pub *>(hub->p0[size_t(p)]);
-			uint64_t soff = 0;
-			for (int q = 0; q < rank; ++q) soff += src->send_cnt[q];
-			for (int a = 0; a < n_arrays; ++a)
-				if (recv_cnt[p] && !(p == rank && (in_place >> a & 1u)))
-					HIP_CHECK(hipMemcpyAsync(static_cast<char *>(d_recv[a]) + roff * elem[a], static_cast<const char *>(src->d_send[a]) + soff * elem[a],
-					                         size_t(recv_cnt[p]) * elem[a], hipMemcpyDefault, st));
-			roff += recv_cnt[p];
-		}
-		HIP_CHECK(stream_wait(st));
-		hub->barrier();   // the senders' buffers may be reused
-	}
-	struct PubAt { const void *const *d_send; const size_t *elem; const uint64_t *send_off, *send_cnt; };
-	void exchange_at(int n_arrays, const void *const *d_send, void *const *d_recv, const size_t *elem, const uint64_t *send_off, const uint64_t *send_cnt,
-	                 const uint64_t *recv_off, const uint64_t *recv_cnt, hipStream_t st, uint32_t in_place = 0) override {
-		HIP_CHECK(stream_wait(st));   // the pieces the peers copy were written before this point of `st`
-		PubAt pub{d_send, elem, send_off, send_cnt};
-		hub->p0[size_t(rank)] = &pub;
-		hub->barrier();
-		for (int p = 0; p < world; ++p) {
-			const PubAt *src = static_cast<const PubAt *>(hub->p0[size_t(p)]);
-			if (src->send_cnt[rank] != recv_cnt[p]) throw DeviceError("chunked exchange: a peer's piece differs from the agreed size");
-			for (int a = 0; a < n_arrays; ++a)
-				if (recv_cnt[p] && !(p == rank && (in_place >> a & 1u)))
-					HIP_CHECK(hipMemcpyAsync(static_cast<char *>(d_recv[a]) + recv_off[p] * elem[a], static_cast<const char *>(src->d_send[a]) + src->send_off[rank] * elem[a],
-					                         size_t(recv_cnt[p]) * elem[a], hipMemcpyDefault, st));
-		}
-		HIP_CHECK(stream_wait(st));
-		hub->barrier();   // the senders' buffers may be reused
-	}
-	void gather_host(const void *mine, size_t bytes, void *all) override {
-		hub->p0[size_t(rank)] = mine;
-		hub->barrier();
-		for (int p = 0; p < world; ++p) std::memcpy(static_cast<char *>(all) + size_t(p) * bytes, hub->p0[size_t(p)], bytes);
-		hub->barrier();
-	}
-	void gather_dev(const void *d_mine, void *d_all, const size_t *off, const size_t *bytes, hipStream_t st) override {
-		HIP_CHECK(stream_wait(st));   // what the peers are about to read was produced on this stream
-		hub->p1[size_t(rank)] = d_mine;
-		hub->barrier();
-		for (int p = 0; p < world; ++p)
-			if (bytes[p]) HIP_CHECK(hipMemcpyAsync(static_cast<char *>(d_all) + off[p], hub->p1[size_t(p)], bytes[p], hipMemcpyDefault, st));
-		HIP_CHECK(stream_wait(st));
-		hub->barrier();
-	}
-	void barrier() override { hub->barrier(); }
-	void *shared_host(int slot, size_t bytes, void **d_ptr) override {
-		hub->barrier();
-		if (rank == 0) {
-			LocalHub::Shared &s = hub->shared[slot];
-			if (s.bytes < bytes) {
-				if (s.host) HIP_CHECK(hipHostFree(s.host));
-				s.host = nullptr; s.bytes = 0;
-				const size_t cap = bytes + bytes / 4 + 4096;
-				HIP_CHECK(hipHostMalloc(&s.host, cap, hipHostMallocPortable | hipHostMallocMapped));
-				s.bytes = cap;
-			}
-		}
-		hub->barrier();
-		void *host = hub->shared[slot].host;
-		HIP_CHECK(hipHostGetDevicePointer(d_ptr, host, 0));
-		return host;
-	}
-};
-
-// The small host tables of the processes of one node meet in shared memory, not on the device: a pass makes a dozen host collectives of
-// a few bytes to a few hundred KB, and each one staged through the GPU (copy in, ncclAllGather, copy out, stream wait) costs ~50-100 us
-// of launch and synchronisation latency whatever its size.  HostMailbox: one POSIX shm object per run (named by the run's unique id;
-// rank 0 creates it, the others attach, rank 0 unlinks it once all are in), `world` slots of SLOT bytes, twice (two halves used in
-// turn), and a sense-reversing barrier on an atomic counter.  A gather = write my slot, barrier, read all slots: ONE barrier -- a rank
-// can only be two collectives ahead of another when that one has passed the barrier in between, i.e. has finished reading the half
-// about to be overwritten.  Payloads beyond SLOT bytes take the RCCL path.  A rank that does not arrive within TIMEOUT_S (a peer died)
-// fails the collective instead of hanging.
-struct HostMailbox {
-	static constexpr size_t SLOT = size_t(1) << 20;
-	// seconds a rank waits for the others (attach, barrier) before it fails the collective for everybody; DROPEST_MAILBOX_TIMEOUT_S (tests)
-	static unsigned timeout_s() { static const unsigned t = [] { const char *e = getenv("DROPEST_MAILBOX_TIMEOUT_S"); return e ? unsigned(std::max(1, atoi(e))) : 300u; }(); return t; }
-	struct Header { std::atomic<uint32_t> attached, arrived, generation, failed; std::atomic<uint64_t> magic; };
-	static uint64_t magic_of(uint64_t token) { return mix64(token ^ 0x6d61696c626f7821ull) | 1ull; }   // never 0: a fresh object reads as zeros
-	int rank = 0, world = 1;
-	char *base = nullptr;
-	size_t bytes = 0;
-	uint64_t phase = 0;
-	Header *hdr() const { return reinterpret_cast<Header *>(base); }
-	char *slot(uint64_t ph, int p) const { return base + 4096 + ((ph & 1) * size_t(world) + size_t(p)) * SLOT; }
-	HostMailbox(uint64_t token, int r, int w) : rank(r), world(w) {
-		bytes = 4096 + 2 * size_t(w) * SLOT;
-		char path[96];
-		std::snprintf(path, sizeof(path), "/dropest_mb_%llx_%d", (unsigned long long)token, w);
-		int fd = -1;
-		const auto t0 = std::chrono::steady_clock::now();
-		if (r == 0) {
-			shm_unlink(path);   // a leftover of a crashed run with the same id cannot be ours
-			fd = shm_open(path, O_CREAT | O_EXCL | O_RDWR, 0600);
-			if (fd < 0 || ftruncate(fd, off_t(bytes)) != 0) { if (fd >= 0) { close(fd); shm_unlink(path); } throw DeviceError("cannot create the host mailbox in /dev/shm"); }
-		} else {
-			for (;;) {   // rank 0 may not be there yet; a file that exists but is not sized yet is not ready either
-				fd = shm_open(path, O_RDWR, 0600);
-				if (fd >= 0) { struct stat st; if (fstat(fd, &st) == 0 && size_t(st.st_size) >= bytes) break; close(fd); fd = -1; }
-				if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(timeout_s())) throw DeviceError("host mailbox: rank 0 did not create it");
-				usleep(200);
-			}
-		}
-		void *m = mmap(nullptr, bytes, PROT_READ | PROT_WRITE, MAP_SHARED, fd, 0);
-		close(fd);
-		if (m == MAP_FAILED) { if (r == 0) shm_unlink(path); throw DeviceError("cannot map the host mailbox"); }
-		base = static_cast<char *>(m);   // (a fresh shm object reads as zeros: the header starts at 0 / 0 / 0 / 0)
-		// rank 0 signs the object it has just created; the others attach only to a signed one (an object of the same name that rank 0 is
-		// about to unlink and replace -- a leftover -- never carries this run's word)
-		// (a wait that times out leaves the constructor by an exception: no destructor runs, so the mapping -- and on rank 0 the name, which
-		// is otherwise unlinked only once everybody is in -- are released here)
-		try {
-			if (r == 0) hdr()->magic.store(magic_of(token), std::memory_order_release);
-			else wait_until([&] { return hdr()->magic.load(std::memory_order_acquire) == magic_of(token); }, "signature", false);
-			hdr()->attached.fetch_add(1, std::memory_order_acq_rel);
-			wait_until([&] { return hdr()->attached.load(std::memory_order_acquire) >= uint32_t(world); }, "attach");
-		} catch (...) {
-			munmap(base, bytes); base = nullptr;
-			if (r == 0) shm_unlink(path);
-			throw;
-		}
-		if (r == 0) shm_unlink(path);   // the mappings keep it alive; nothing is left behind on a crash
-	}
-	~HostMailbox() { if (base) munmap(base, bytes); }
-	HostMailbox(const HostMailbox &) = delete;
-	template <class F> void wait_until(F &&done, const char *what, bool heed_failed = true) {
-		const auto t0 = std::chrono::steady_clock::now();
-		for (uint32_t spins = 0; !done(); ++spins) {
-			if (heed_failed && hdr()->failed.load(std::memory_order_acquire)) throw DeviceError("another shard of the run failed");
-			if (spins < 2000) { dropest::host_cpu_relax(); continue; }
-			sched_yield();
-			if ((spins & 1023u) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(timeout_s())) {
-				hdr()->failed.store(1, std::memory_order_release);
-				throw DeviceError(std::string("host mailbox: a shard did not arrive (") + what + ")");
-			}
-		}
-	}
-	void fail() { if (base) hdr()->failed.store(1, std::memory_order_release); }
-	void barrier() {
-		Header *h = hdr();
-		const uint32_t g = h->generation.load(std::memory_order_acquire);
-		if (h->arrived.fetch_add(1, std::memory_order_acq_rel) + 1 == uint32_t(world)) {
-			h->arrived.store(0, std::memory_order_relaxed);
-			h->generation.store(g + 1, std::memory_order_release);
-			return;
-		}
-		wait_until([&] { return h->generation.load(std::memory_order_acquire) != g; }, "barrier");
-	}
-	bool fits(size_t n) const { return n <= SLOT; }
-	void gather(const void *mine, size_t n, void *all) {   // n <= SLOT, the same on every rank
-		const uint64_t ph = phase++;
-		if (n) std::memcpy(slot(ph, rank), mine, n);
-		barrier();
-		for (int p = 0; p < world; ++p) if (n) std::memcpy(static_cast<char *>(all) + size_t(p) * n, slot(ph, p), n);
-	}
-};
-
-// One process per GPU: RCCL for the device data; the small host tables through the HostMailbox above (RCCL all-gathers of staged bytes
-// for payloads beyond its slots, or for everything with DROPEST_HOST_COLLECTIVES=rccl).  Shared host memory for the results: a POSIX
-// shm object mapped and registered by every process of the node.
-struct RcclTransport : Transport {
-	ncclComm_t comm = nullptr;
-	hipStream_t st0 = nullptr;          // the owning context's stream
-	DevBuf<unsigned char> stage_in, stage_out;
-	PinnedBuf<unsigned char> h_in, h_out;
-	uint64_t token = 0;
-	std::unique_ptr<HostMailbox> mailbox;
-	struct Shm { void *host = nullptr; size_t bytes = 0; int gen = 0; } shm[4];
-	// DROPEST_SHARD_DATAPLANE=shm: the device data of the collectives (exchange, gather_dev) crosses through POSIX shared memory instead of
-	// RCCL -- every process stages what it sends in a segment of its own, the peers read it after a barrier.  For runs whose processes
-	// share GPUs (RCCL refuses two ranks on one device): the multi-process tests on a one-GPU box run the whole step this way -- the
-	// mailbox, the shared result buffers, the sequence of collectives are the real ones, only ncclSend / ncclRecv are stood in for.
-	bool shm_plane = false;
-	struct Stage { void *host = nullptr; size_t bytes = 0; uint64_t gen = 0; };
-	Stage my_stage;
-	std::vector<Stage> peer_stage;
-	static void stage_path(char *out, size_t n, uint64_t token, int rank, uint64_t gen) { std::snprintf(out, n, "/dropest_dp_%llx_%d_%llu", (unsigned long long)token, rank, (unsigned long long)gen); }
-	// collective: every rank makes sure its segment holds `need` bytes, then maps the peers' segments (again) where they were replaced
-	void stage_prepare(size_t need) {
-		uint64_t row[2] = {my_stage.gen, 0};
-		if (need > my_stage.bytes) {
-			if (my_stage.host) { char old[128]; stage_path(old, sizeof(old), token, rank, my_stage.gen); munmap(my_stage.host, my_stage.bytes); shm_unlink(old); my_stage.host = nullptr; }
-			const size_t cap = need + need / 4 + 4096;
-			char path[128];
-			stage_path(path, sizeof(path), token, rank, my_stage.gen + 1);
-			shm_unlink(path);
-			const int fd = shm_open(path, O_CREAT | O_EXCL | O_RDWR, 0600);
-			if (fd < 0 || posix_fallocate(fd, 0, off_t(cap)) != 0) { if (fd >= 0) { close(fd); shm_unlink(path); } throw DeviceError("cannot create the staging segment of the shm data plane"); }
-			void *m = mmap(nullptr, cap, PROT_READ | PROT_WRITE, MAP_SHARED, fd, 0);
-			close(fd);
-			if (m == MAP_FAILED) { shm_unlink(path); throw DeviceError("cannot map the staging segment of the shm data plane"); }
-			my_stage.host = m; my_stage.bytes = cap; ++my_stage.gen;
-			row[0] = my_stage.gen;
-		}
-		row[1] = my_stage.bytes;
-		std::vector<uint64_t> all(size_t(world) * 2);
-		gather_host(row, 16, all.data());
-		peer_stage.resize(size_t(world));
-		for (int p = 0; p < world; ++p) {
-			if (p == rank) continue;
-			Stage &ps = peer_stage[size_t(p)];
-			if (ps.gen == all[size_t(p) * 2] && ps.host) continue;
-			if (ps.host) { munmap(ps.host, ps.bytes); ps.host = nullptr; }
-			ps.gen = all[size_t(p) * 2]; ps.bytes = size_t(all[size_t(p) * 2 + 1]);
-			if (!ps.gen) continue;
-			char path[128];
-			stage_path(path, sizeof(path), token, p, ps.gen);
-			const int fd = shm_open(path, O_RDONLY, 0600);
-			void *m = fd >= 0 ? mmap(nullptr, ps.bytes, PROT_READ, MAP_SHARED, fd, 0) : MAP_FAILED;
-			if (fd >= 0) close(fd);
-			if (m == MAP_FAILED) throw DeviceError("cannot map a peer's staging segment of the shm data plane");
-			ps.host = m;
-		}
-	}
-	RcclTransport(int r, int w, const uint8_t id_bytes[128], hipStream_t st) : st0(st) {
-		rank = r; world = w;
-		for (int i = 0; i < 128; ++i) token = token * 1099511628211ull + id_bytes[i];
-		{ const char *dp = getenv("DROPEST_SHARD_DATAPLANE"); shm_plane = dp && std::string(dp) == "shm"; }
-		if (shm_plane) { mailbox = std::make_unique<HostMailbox>(token, r, w); return; }   // one host by construction; no communicator
-		const RcclApi &api = RcclApi::get();
-		ncclUniqueId id;
-		static_assert(sizeof(id) == 128, "ncclUniqueId");
-		std::memcpy(&id, id_bytes, 128);
-		api.check(api.CommInitRank(&comm, w, id, r), "ncclCommInitRank");
-		const char *hc = getenv("DROPEST_HOST_COLLECTIVES");
-		bool use_mailbox = !(hc && std::string(hc) == "rccl");
-		if (use_mailbox && w > 1) {
-			// The mailbox is POSIX shared memory: every rank must be on ONE host.  The ranks compare a word that names the host's running
-			// kernel instance (boot id, else the host name) over the communicator first; ranks on several hosts keep the RCCL path for
-			// their host collectives instead of waiting 300 s for a shm object that will never show up.
-			uint64_t mine = 1469598103934665603ull;
-			auto fold = [&](const char *s) { for (; *s; ++s) { mine ^= (unsigned char)*s; mine *= 1099511628211ull; } };
-			char buf[256] = {0};
-			if (FILE *f = fopen("/proc/sys/kernel/random/boot_id", "r")) { if (fgets(buf, sizeof(buf), f)) fold(buf); fclose(f); }
-			if (!buf[0] && gethostname(buf, sizeof(buf) - 1) == 0) fold(buf);
-			std::vector<uint64_t> all(size_t(w), 0);
-			gather_host(&mine, 8, all.data());   // (no mailbox yet: the staged RCCL all-gather)
-			for (int p = 0; p < w; ++p) use_mailbox &= all[size_t(p)] == mine;
-		}
-		if (use_mailbox) mailbox = std::make_unique<HostMailbox>(token, r, w);
-	}
-	~RcclTransport() override {
-		for (auto &ps : peer_stage) if (ps.host) munmap(ps.host, ps.bytes);
-		if (my_stage.host) { char path[128]; stage_path(path, sizeof(path), token, rank, my_stage.gen); munmap(my_stage.host, my_stage.bytes); shm_unlink(path); }
-		for (auto &s : shm) if (s.host) { (void)hipHostUnregister(s.host); munmap(s.host, s.bytes); }
-		if (comm) (void)RcclApi::get().CommDestroy(comm);
-	}
-	const char *name() const override { return shm_plane ? "shm" : "rccl"; }
-	// the shm data plane's all-to-all(v): [header: my send counts][array 0, all destinations][array 1 ...] in my segment, a barrier, then
-	// every rank copies the blocks addressed to it out of its peers' segments
-	void exchange_shm(int n_arrays, const void *const *d_send, void *const *d_recv, const size_t *elem, const uint64_t *send_cnt,
-	                  const uint64_t *recv_cnt, hipStream_t st) {
-		uint64_t total = 0;
-		for (int p = 0; p < world; ++p) total += send_cnt[p];
-		size_t need = size_t(world) * 8;
-		for (int a = 0; a < n_arrays; ++a) need += ((size_t(total) * elem[a] + 63) & ~size_t(63));
-		stage_prepare(need);
-		char *mine = static_cast<char *>(my_stage.host);
-		std::memcpy(mine, send_cnt, size_t(world) * 8);
-		size_t at = size_t(world) * 8;
-		HIP_CHECK(stream_wait(st));   // what is sent was produced on this stream
-		for (int a = 0; a < n_arrays; ++a) {
-			if (total) HIP_CHECK(hipMemcpy(mine + at, d_send[a], size_t(total) * elem[a], hipMemcpyDeviceToHost));
-			at += (size_t(total) * elem[a] + 63) & ~size_t(63);
-		}
-		barrier();
-		uint64_t roff = 0;
-		for (int p = 0; p < world; ++p) {
-			if (p != rank && recv_cnt[p]) {
-				const char *peer = static_cast<const char *>(peer_stage[size_t(p)].host);
-				const uint64_t *pc = reinterpret_cast<const uint64_t *>(peer);
-				uint64_t ptotal = 0, poff = 0;
-				for (int q = 0; q < world; ++q) { if (q < rank) poff += pc[q]; ptotal += pc[q]; }
-				if (pc[rank] != recv_cnt[p]) throw DeviceError("shm data plane: a peer's send count differs from the agreed one");
-				size_t pat = size_t(world) * 8;
-				for (int a = 0; a < n_arrays; ++a) {
-					HIP_CHECK(hipMemcpy(static_cast<char *>(d_recv[a]) + roff * elem[a], peer + pat + size_t(poff) * elem[a], size_t(recv_cnt[p]) * elem[a], hipMemcpyHostToDevice));
-					pat += (size_t(ptotal) * elem[a] + 63) & ~size_t(63);
-				}
-			}
-			roff += recv_cnt[p];
-		}
-		barrier();   // nobody overwrites its segment while a peer still reads it
-	}
-	void exchange(int n_arrays, const void *const *d_send, void *const *d_recv, const size_t *elem, const uint64_t *send_cnt,
-	              const uint64_t *recv_cnt, hipStream_t st, uint32_t in_place = 0) override {
-		if (shm_plane) {
-			uint64_t soff = 0, roff = 0;
-			for (int p = 0; p < rank; ++p) { soff += send_cnt[p]; roff += recv_cnt[p]; }
-			for (int a = 0; a < n_arrays; ++a)
-				if (send_cnt[rank] && !(in_place >> a & 1u)) HIP_CHECK(hipMemcpyAsync(static_cast<char *>(d_recv[a]) + roff * elem[a], static_cast<const char *>(d_send[a]) + soff * elem[a],
-				                                             size_t(send_cnt[rank]) * elem[a], hipMemcpyDeviceToDevice, st));
-			exchange_shm(n_arrays, d_send, d_recv, elem, send_cnt, recv_cnt, st);
-			HIP_CHECK(stream_wait(st));
-			return;
-		}
-		const RcclApi &api = RcclApi::get();
-		// the block a shard keeps never leaves the device: a plain copy (a self send / recv pair moves it at a fifth of the rate)
-		{
-			uint64_t soff = 0, roff = 0;
-			for (int p = 0; p < rank; ++p) { soff += send_cnt[p]; roff += recv_cnt[p]; }
-			for (int a = 0; a < n_arrays; ++a)
-				if (send_cnt[rank] && !(in_place >> a & 1u)) HIP_CHECK(hipMemcpyAsync(static_cast<char *>(d_recv[a]) + roff * elem[a], static_cast<const char *>(d_send[a]) + soff * elem[a],
-				                                             size_t(send_cnt[rank]) * elem[a], hipMemcpyDeviceToDevice, st));
-		}
-		api.check(api.GroupStart(), "ncclGroupStart");
-		for (int a = 0; a < n_arrays; ++a) {
-			uint64_t soff = 0, roff = 0;
-			for (int p = 0; p < world; ++p) {
-				if (p == rank) { soff += send_cnt[p]; roff += recv_cnt[p]; continue; }
-				if (send_cnt[p]) api.check(api.Send(static_cast<const char *>(d_send[a]) + soff * elem[a], size_t(send_cnt[p]) * elem[a], ncclUint8, p, comm, st), "ncclSend");
-				if (recv_cnt[p]) api.check(api.Recv(static_cast<char *>(d_recv[a]) + roff * elem[a], size_t(recv_cnt[p]) * elem[a], ncclUint8, p, comm, st), "ncclRecv");
-				soff += send_cnt[p]; roff += recv_cnt[p];
-			}
-		}
-		api.check(api.GroupEnd(), "ncclGroupEnd");
-		// (no wait here: whatever reads the received blocks is queued behind them on this stream -- cb_sample, cb_insert --, and the send
-		// buffers are not rewritten before the next pass's partition, on this stream too)
-	}
-	void exchange_at(int n_arrays, const void *const *d_send, void *const *d_recv, const size_t *elem, const uint64_t *send_off, const uint64_t *send_cnt,
-	                 const uint64_t *recv_off, const uint64_t *recv_cnt, hipStream_t st, uint32_t in_place = 0) override {
-		for (int a = 0; a < n_arrays; ++a)   // the piece a shard keeps never leaves the device
-			if (send_cnt[rank] && !(in_place >> a & 1u))
-				HIP_CHECK(hipMemcpyAsync(static_cast<char *>(d_recv[a]) + recv_off[rank] * elem[a], static_cast<const char *>(d_send[a]) + send_off[rank] * elem[a],
-				                         size_t(send_cnt[rank]) * elem[a], hipMemcpyDeviceToDevice, st));
-		if (shm_plane) {   // processes that share GPUs: the pieces cross through the staging segments, with the host in between
-			uint64_t total = 0;
-			for (int p = 0; p < world; ++p) total += p == rank ? 0 : send_cnt[p];
-			size_t need = size_t(world) * 16;
-			for (int a = 0; a < n_arrays; ++a) need += ((size_t(total) * elem[a] + 63) & ~size_t(63));
-			stage_prepare(need);
-			char *mine = static_cast<char *>(my_stage.host);
-			// header: for every peer, where its piece starts in each array's staged run (in elements) and its length
-			uint64_t *hdr = reinterpret_cast<uint64_t *>(mine);
-			uint64_t run = 0;
-			for (int p = 0; p < world; ++p) { hdr[2 * p] = run; hdr[2 * p + 1] = p == rank ? 0 : send_cnt[p]; run += hdr[2 * p + 1]; }
-			HIP_CHECK(stream_wait(st));
-			size_t at = size_t(world) * 16;
-			for (int a = 0; a < n_arrays; ++a) {
-				for (int p = 0; p < world; ++p)
-					if (p != rank && send_cnt[p])
-						HIP_CHECK(hipMemcpy(mine + at + size_t(hdr[2 * p]) * elem[a], static_cast<const char *>(d_send[a]) + send_off[p] * elem[a], size_t(send_cnt[p]) * elem[a], hipMemcpyDeviceToHost));
-				at += (size_t(total) * elem[a] + 63) & ~size_t(63);
-			}
-			barrier();
-			for (int p = 0; p < world; ++p) {
-				if (p == rank || !recv_cnt[p]) continue;
-				const char *peer = static_cast<const char *>(peer_stage[size_t(p)].host);
-				const uint64_t *ph = reinterpret_cast<const uint64_t *>(peer);
-				if (ph[2 * rank + 1] != recv_cnt[p]) throw DeviceError("shm data plane: a peer's piece differs from the agreed size");
-				uint64_t ptotal = 0;
-				for (int q = 0; q < world; ++q) ptotal += ph[2 * q + 1];
-				size_t pat = size_t(world) * 16;
-				for (int a = 0; a < n_arrays; ++a) {
-					HIP_CHECK(hipMemcpy(static_cast<char *>(d_recv[a]) + recv_off[p] * elem[a], peer + pat + size_t(ph[2 * rank]) * elem[a], size_t(recv_cnt[p]) * elem[a], hipMemcpyHostToDevice));
-					pat += (size_t(ptotal) * elem[a] + 63) & ~size_t(63);
-				}
-			}
-			barrier();   // nobody overwrites its segment while a peer still reads it
-			return;
-		}
-		const RcclApi &api = RcclApi::get();
-		api.check(api.GroupStart(), "ncclGroupStart");
-		for (int a = 0; a < n_arrays; ++a)
-			for (int p = 0; p < world; ++p) {
-				if (p == rank) continue;
-				if (send_cnt[p]) api.check(api.Send(static_cast<const char *>(d_send[a]) + send_off[p] * elem[a], size_t(send_cnt[p]) * elem[a], ncclUint8, p, comm, st), "ncclSend");
-				if (recv_cnt[p]) api.check(api.Recv(static_cast<char *>(d_recv[a]) + recv_off[p] * elem[a], size_t(recv_cnt[p]) * elem[a], ncclUint8, p, comm, st), "ncclRecv");
-			}
-		api.check(api.GroupEnd(), "ncclGroupEnd");
-	}
-	void gather_host(const void *mine, size_t bytes, void *all) override {
-		if (mailbox && mailbox->fits(bytes)) { mailbox->gather(mine, bytes, all); return; }
-		if (shm_plane) {   // no communicator: a payload beyond a slot goes through the mailbox slot by slot
-			std::vector<unsigned char> part(HostMailbox::SLOT * size_t(world));
-			for (size_t at = 0; at < bytes; at += HostMailbox::SLOT) {
-				const size_t n = std::min(HostMailbox::SLOT, bytes - at);
-				mailbox->gather(static_cast<const char *>(mine) + at, n, part.data());
-				for (int p = 0; p < world; ++p) std::memcpy(static_cast<char *>(all) + size_t(p) * bytes + at, part.data() + size_t(p) * n, n);
-			}
-			return;
-		}
-		const RcclApi &api = RcclApi::get();
-		const size_t b = std::max<size_t>(bytes, 1);
-		stage_in.ensure(b); stage_out.ensure(b * size_t(world)); h_in.ensure(b); h_out.ensure(b * size_t(world));
-		std::memcpy(h_in.p, mine, bytes);
-		HIP_CHECK(hipMemcpyAsync(stage_in.p, h_in.p, b, hipMemcpyHostToDevice, st0));
-		api.check(api.AllGather(stage_in.p, stage_out.p, b, ncclUint8, comm, st0), "ncclAllGather");
-		HIP_CHECK(hipMemcpyAsync(h_out.p, stage_out.p, b * size_t(world), hipMemcpyDeviceToHost, st0));
-		HIP_CHECK(stream_wait(st0));
-		for (int p = 0; p < world; ++p) std::memcpy(static_cast<char *>(all) + size_t(p) * bytes, h_out.p + size_t(p) * b, bytes);
-	}
-	void gather_dev(const void *d_mine, void *d_all, const size_t *off, const size_t *bytes, hipStream_t st) override {
-		if (shm_plane) {
-			stage_prepare(bytes[rank] + 64);
-			HIP_CHECK(stream_wait(st));
-			if (bytes[rank]) HIP_CHECK(hipMemcpy(my_stage.host, d_mine, bytes[rank], hipMemcpyDeviceToHost));
-			barrier();
-			for (int p = 0; p < world; ++p) {
-				if (!bytes[p]) continue;
-				if (p == rank) HIP_CHECK(hipMemcpy(static_cast<char *>(d_all) + off[p], d_mine, bytes[p], hipMemcpyDeviceToDevice));
-				else HIP_CHECK(hipMemcpy(static_cast<char *>(d_all) + off[p], peer_stage[size_t(p)].host, bytes[p], hipMemcpyHostToDevice));
-			}
-			barrier();
-			return;
-		}
-		const RcclApi &api = RcclApi::get();
-		api.check(api.GroupStart(), "ncclGroupStart");
-		for (int p = 0; p < world; ++p) {
-			if (bytes[rank]) api.check(api.Send(d_mine, bytes[rank], ncclUint8, p, comm, st), "ncclSend");
-			if (bytes[p]) api.check(api.Recv(static_cast<char *>(d_all) + off[p], bytes[p], ncclUint8, p, comm, st), "ncclRecv");
-		}
-		api.check(api.GroupEnd(), "ncclGroupEnd");   // (stream-ordered like exchange(): the kernels that read d_all follow on `st`)
-	}
-	void barrier() override { unsigned char x = 0; std::vector<unsigned char> all(static_cast<size_t>(world)); gather_host(&x, 1, all.data()); }
-	void *shared_host(int slot, size_t bytes, void **d_ptr) override {
-		Shm &s = shm[slot];
-		// every rank must take the same branch: agree on the capacity first
-		uint64_t want = s.bytes >= bytes ? 0 : uint64_t(bytes + bytes / 4 + 4096);
-		std::vector<uint64_t> wants(static_cast<size_t>(world));
-		gather_host(&want, 8, wants.data());
-		uint64_t cap = 0;
-		for (uint64_t w : wants) cap = std::max(cap, w);
-		if (cap) {
-			cap = std::max<uint64_t>(cap, s.bytes);
-			if (s.host) { HIP_CHECK(hipHostUnregister(s.host)); munmap(s.host, s.bytes); s.host = nullptr; s.bytes = 0; }
-			++s.gen;
-			uint64_t pid0 = uint64_t(getpid());
-			std::vector<uint64_t> pids(static_cast<size_t>(world));
-			gather_host(&pid0, 8, pids.data());
-			char path[128];
-			std::snprintf(path, sizeof(path), "/dropest_%llx_%llu_%d_%d", (unsigned long long)token, (unsigned long long)pids[0], slot, s.gen);
-			uint64_t ok = 1;
-			int fd = -1;
-			if (rank == 0) {
-				fd = shm_open(path, O_CREAT | O_EXCL | O_RDWR, 0600);
-				// The pages are reserved now (a full tmpfs fails here, not with SIGBUS later) -- on the NUMA node of this rank's GPU, where ROCm
-				// puts pinned host memory and where the threads that widen the matrices into this buffer run (matrix_decode.h): left to the
-				// default policy they land on whatever node this thread happens to run on, and every slot is then written across the sockets.
-				h_in.ensure(4096);
-				const int node = dropest::numa_node_of(h_in.p);
-				unsigned long mask[16] = {0};
-				const bool bound = node >= 0 && node < 1024 && (mask[node / 64] |= 1ul << (node % 64), syscall(SYS_set_mempolicy, 1 /* MPOL_PREFERRED */, mask, 1024ul) == 0);
-				if (fd < 0 || posix_fallocate(fd, 0, off_t(cap)) != 0) ok = 0;
-				if (bound) (void)syscall(SYS_set_mempolicy, 0 /* MPOL_DEFAULT */, nullptr, 0ul);
-			}
-			std::vector<uint64_t> oks(static_cast<size_t>(world));
-			gather_host(&ok, 8, oks.data());
-			if (!oks[0]) { if (fd >= 0) { close(fd); shm_unlink(path); } throw DeviceError("cannot reserve the shared result buffer in /dev/shm"); }
-			if (rank != 0) fd = shm_open(path, O_RDWR, 0600);
-			void *host = fd >= 0 ? mmap(nullptr, size_t(cap), PROT_READ | PROT_WRITE, MAP_SHARED, fd, 0) : MAP_FAILED;
-			if (fd >= 0) close(fd);
-			ok = host != MAP_FAILED && hipHostRegister(host, size_t(cap), hipHostRegisterMapped | hipHostRegisterPortable) == hipSuccess;
-			gather_host(&ok, 8, oks.data());
-			if (rank == 0) shm_unlink(path);   // the mappings keep it alive; nothing is left behind on a crash
-			for (uint64_t o : oks) if (!o) throw DeviceError("cannot map / register the shared result buffer");
-			s.host = host; s.bytes = size_t(cap);
-		}
-		HIP_CHECK(hipHostGetDevicePointer(d_ptr, s.host, 0));
-		return s.host;
-	}
-};
-
-// ---- small kernels ---------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void take_u32_kernel(const uint32_t *__restrict__ table, const uint32_t *__restrict__ pos, uint32_t n, uint32_t *__restrict__ out) {
-	const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-	if (i < n) out[i] = table[pos[i]];
-}
-__global__ __launch_bounds__(256) void gather_u32_rows_kernel(const uint32_t *__restrict__ in, const uint32_t *__restrict__ row, uint32_t n, uint32_t width,
-                                                              uint32_t *__restrict__ out) {
-	for (uint64_t k = uint64_t(blockIdx.x) * 256 + threadIdx.x; k < uint64_t(n) * width; k += uint64_t(gridDim.x) * 256)
-		out[k] = in[uint64_t(row[k / width]) * width + k % width];
-}
-struct ImportGatherArgs { const uint32_t *row; uint32_t n; const unsigned long long *low_all; const uint32_t *col_all[4]; unsigned long long *o_low; uint32_t *o_col[4]; };
-__global__ __launch_bounds__(256) void import_gather_kernel(ImportGatherArgs a) {
-	const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-	if (i >= a.n) return;
-	const uint32_t r = a.row[i];
-	a.o_low[i] = a.low_all[r];
-#pragma unroll
-	for (int k = 0; k < 4; ++k) a.o_col[k][i] = a.col_all[k][r];
-}
-// desc[3c .. 3c+2] = (src_start, dst_start, len) of column c; rows / values go to their places in the global matrix
-__global__ __launch_bounds__(256) void place_columns_kernel(const unsigned long long *__restrict__ desc, const uint32_t *__restrict__ src_rows,
-                                                            const uint32_t *__restrict__ src_vals, uint32_t *__restrict__ dst_rows, uint32_t *__restrict__ dst_vals) {
-	const unsigned long long s = desc[3ull * blockIdx.x], d = desc[3ull * blockIdx.x + 1], len = desc[3ull * blockIdx.x + 2];
-	for (unsigned long long t = threadIdx.x; t < len; t += 256) { dst_rows[d + t] = src_rows[s + t]; dst_vals[d + t] = src_vals[s + t]; }
-}
-// The same, narrowing on the way out (16-bit row indices and values: half the bytes over this shard's PCIe link); a value beyond
-// 65534 is stored as 0xFFFF and listed exactly with its GLOBAL entry index (ovf[0] = count, then (position lo, position hi,
-// value) triples, at most ovf_cap of them).
-__global__ __launch_bounds__(256) void place_columns_narrow_kernel(const unsigned long long *__restrict__ desc, const uint32_t *__restrict__ src_rows,
-                                                                   const uint32_t *__restrict__ src_vals, uint16_t *__restrict__ dst_rows, uint16_t *__restrict__ dst_vals,
-                                                                   uint32_t *__restrict__ ovf, uint32_t ovf_cap) {
-	const unsigned long long s = desc[3ull * blockIdx.x], d = desc[3ull * blockIdx.x + 1], len = desc[3ull * blockIdx.x + 2];
-	for (unsigned long long t = threadIdx.x; t < len; t += 256) {
-		const uint32_t v = src_vals[s + t];
-		dst_rows[d + t] = uint16_t(src_rows[s + t]);
-		dst_vals[d + t] = v >= 0xFFFFu ? uint16_t(0xFFFFu) : uint16_t(v);
-		if (v >= 0xFFFFu) {
-			const uint32_t at = atomicAdd(ovf, 1u);
-			if (at < ovf_cap) { ovf[1 + 3 * at] = uint32_t(d + t); ovf[2 + 3 * at] = uint32_t((d + t) >> 32); ovf[3 + 3 * at] = v; }
-		}
-	}
-}
-// The BYTE form (dropest_matrix_bytes, include/dropest_amd.h): u8 row delta + u8 value at the entry's GLOBAL place, two bytes per entry
-// on the PCIe link.  A workgroup takes one column.  A lane takes SIXTEEN consecutive entries of an aligned group: a group that lies inside
-// the column leaves as one 16-byte store per array (a wave writes 1 KB of each array in one piece: the link takes whole lines -- with
-// 4-byte stores per lane the placing kernels of a C2 pass reached ~30 GB/s of the link's ~52), the ragged groups at a column's ends byte by
-// byte (the neighbouring column may be another shard's).  Entries that do not fit a byte (255 = listed) go to this shard's segment of the
-// shared buffer with their global position: a wave counts what its lanes list, takes its places with ONE atomic per kind on the shard's
-// counters, and the lanes write their entries there (no LDS, no workgroup barrier); the readers concatenate the segments (the lists
-// carry no order).
-__global__ __launch_bounds__(256) void place_columns_bytes_kernel(const unsigned long long *__restrict__ desc, const uint32_t *__restrict__ src_rows,
-                                                                  const uint32_t *__restrict__ src_vals, uint8_t *__restrict__ dst_delta,
-                                                                  uint8_t *__restrict__ dst_val, uint32_t *__restrict__ counters /* [2] */,
-                                                                  uint32_t *__restrict__ rl_pos, uint32_t *__restrict__ rl_row,
-                                                                  uint32_t *__restrict__ vl_pos, uint32_t *__restrict__ vl_val, uint32_t cap,
-                                                                  uint32_t *__restrict__ slot_rows = nullptr, uint32_t *__restrict__ slot_vals = nullptr,
-                                                                  uint32_t *flag = nullptr, uint32_t epoch = 0) {
-	// flag / epoch (matrix_decode.h): the arrival flag of the chunk of columns placed BEFORE this launch on the stream -- this kernel runs, so
-	// that chunk is complete and visible to the host threads that widen it into the 32-bit slots.  slot_rows / slot_vals: the slots
-	// themselves (node-shared host memory); a listed entry is written there directly, so the widening needs no list at all.
-	if (flag && blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(flag, epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-	const unsigned long long s = desc[3ull * blockIdx.x], d = desc[3ull * blockIdx.x + 1], len = desc[3ull * blockIdx.x + 2];
-	const uint32_t lane = threadIdx.x & 63u;
-	const unsigned long long g0 = d >> 4, g1 = (d + len + 15) >> 4;
-	for (unsigned long long gb = g0; gb < g1; gb += blockDim.x) {   // (256 threads for cm's long columns, one wave for cm_raw's mostly short ones)
-		const unsigned long long gq = gb + threadIdx.x, first = 16 * gq;
-		uint32_t dd[4] = {0, 0, 0, 0}, vv[4] = {0, 0, 0, 0}, inside = 0, n_listed[2] = {0, 0};
-		if (gq < g1) {
-			uint32_t prev = (first > d && first <= d + len) ? src_rows[s + (first - d) - 1] : 0xFFFFFFFFu;
-#pragma unroll
-			for (uint32_t b = 0; b < 16; ++b) {
-				const unsigned long long g = first + b;
-				if (g < d || g >= d + len) continue;
-				const unsigned long long t = g - d;
-				const uint32_t row = src_rows[s + t], v = src_vals[s + t];
-				const uint32_t delta = row - prev;
-				prev = row;
-				inside |= 1u << b;
-				dd[b >> 2] |= (delta >= 255u ? 255u : delta) << (8 * (b & 3u));
-				vv[b >> 2] |= (v >= 255u ? 255u : v) << (8 * (b & 3u));
-				if (delta >= 255u) { ++n_listed[0]; if (slot_rows) slot_rows[g] = row; }
-				if (v >= 255u) { ++n_listed[1]; if (slot_vals) slot_vals[g] = v; }
-			}
-			if (inside == 0xFFFFu) {
-				reinterpret_cast<uint4 *>(dst_delta)[gq] = make_uint4(dd[0], dd[1], dd[2], dd[3]);
-				reinterpret_cast<uint4 *>(dst_val)[gq] = make_uint4(vv[0], vv[1], vv[2], vv[3]);
-			} else {
-#pragma unroll
-				for (uint32_t b = 0; b < 16; ++b) if (inside >> b & 1u) { dst_delta[first + b] = uint8_t(dd[b >> 2] >> (8 * (b & 3u))); dst_val[first + b] = uint8_t(vv[b >> 2] >> (8 * (b & 3u))); }
-			}
-		}
-#pragma unroll
-		for (uint32_t k = 0; k < 2; ++k) {
-			if (!__ballot(n_listed[k] != 0)) continue;
-			const uint32_t incl = wave_incl_scan_u32(n_listed[k]);
-			const uint32_t total = uint32_t(__shfl(int(incl), 63, 64));
-			uint32_t base = 0;
-			if (lane == 0) base = atomicAdd(&counters[k], total);
-			base = uint32_t(__shfl(int(base), 0, 64));
-			uint32_t at = base + incl - n_listed[k];
-			if (n_listed[k]) {
-				uint32_t *pos = k ? vl_pos : rl_pos, *x = k ? vl_val : rl_row;
-				const uint32_t *src = k ? src_vals : src_rows;
-#pragma unroll
-				for (uint32_t b = 0; b < 16; ++b)
-					if ((inside >> b & 1u) && (((k ? vv[b >> 2] : dd[b >> 2]) >> (8 * (b & 3u))) & 0xFFu) == 255u) {
-						if (at < cap) { pos[at] = uint32_t(first + b); x[at] = src[s + (first + b - d)]; }
-						++at;
-					}
-			}
-		}
-	}
-}
-// cm_raw planned on the device (assemble_raw_device): the shards' real cells, each list ascending by the stream ordinal of the cell's
-// first read, merged by rank -- a cell's global column = its local place + the cells of every other shard that come before it.
-struct RawPlanTable { uint32_t world, rank; uint64_t off[64]; uint32_t n[64]; };   // shard s: first[n] at all + off, nnz prefix[n + 1] behind it
-struct QueryTable { uint32_t world; uint64_t in_off[65], part_off[64], out_off[65], first_ord[64]; };
-__global__ __launch_bounds__(256) void answer_queries_kernel(QueryTable t, const uint32_t *__restrict__ q_in, uint32_t n, const uint32_t *__restrict__ part_idx,
-                                                             uint32_t *__restrict__ out) {
-	const uint32_t k = blockIdx.x * 256 + threadIdx.x;
-	if (k >= n) return;
-	uint32_t p = 0;
-	while (p + 1 < t.world && k >= t.in_off[p + 1]) ++p;
-	out[k] = part_idx[t.part_off[p] + q_in[k]];
-}
-__global__ __launch_bounds__(256) void ordinals_from_answers_kernel(QueryTable t, const uint32_t *__restrict__ back, uint32_t n, unsigned long long *__restrict__ first) {
-	const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-	if (i >= n) return;
-	uint32_t s = 0;
-	while (s + 1 < t.world && i >= t.out_off[s + 1]) ++s;
-	first[i] = t.first_ord[s] + back[i];
-}
-__global__ __launch_bounds__(256) void plan_raw_columns_kernel(RawPlanTable t, const unsigned long long *__restrict__ all, const uint32_t *__restrict__ col_cell,
-                                                               const unsigned long long *__restrict__ cell_barcode, uint32_t n,
-                                                               unsigned long long *__restrict__ desc, unsigned long long *__restrict__ colptr64,
-                                                               uint32_t *__restrict__ colptr32, unsigned long long *__restrict__ barcodes,
-                                                               uint32_t *__restrict__ h_begin = nullptr, uint32_t *__restrict__ h_end = nullptr) {
-	const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-	if (i >= n) return;
-	const unsigned long long *mine = all + t.off[t.rank], *my_pre = mine + t.n[t.rank];
-	const unsigned long long f = mine[i];
-	unsigned long long col = i, at = my_pre[i];
-	for (uint32_t s = 0; s < t.world; ++s) {
-		if (s == t.rank) continue;
-		const unsigned long long *fs = all + t.off[s];
-		uint32_t lo = 0, hi = t.n[s];
-		while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (fs[mid] < f) lo = mid + 1; else hi = mid; }
-		col += lo; at += fs[t.n[s] + lo];
-	}
-	desc[3ull * i] = my_pre[i]; desc[3ull * i + 1] = at; desc[3ull * i + 2] = my_pre[i + 1] - my_pre[i];
-	colptr64[col] = at; colptr32[col] = uint32_t(at); barcodes[col] = cell_barcode[col_cell[i]];
-	if (h_begin) { h_begin[i] = uint32_t(at); h_end[i] = uint32_t(at + my_pre[i + 1] - my_pre[i]); }   // (pinned: what the host threads that widen this shard's columns walk by)
-}
-__global__ void copy_words_kernel(const uint32_t *__restrict__ src, uint32_t *__restrict__ dst, uint32_t n) { if (threadIdx.x < n) dst[threadIdx.x] = src[threadIdx.x]; }
-// local read position -> global stream ordinal: position p came from source rank s = the block [recv_off[s], recv_off[s+1])
-// it lies in, as that rank's idx[p]-th resident read
-// (every shard's resident reads are ONE contiguous range of the stream and the ranges ascend with the rank: the blocks a
-// shard receives, concatenated in source-rank order, are then in stream order, which is what makes a read's POSITION
-// on its shard a valid first-seen ordinal there)
-struct OrdinalMap { const uint32_t *idx; uint32_t world; uint64_t recv_off[65]; uint64_t first_ord[64]; };
-__device__ inline unsigned long long to_global_ordinal(const OrdinalMap &m, uint32_t p) {
-	uint32_t s = 0;
-	while (s + 1 < m.world && p >= m.recv_off[s + 1]) ++s;
-	return m.first_ord[s] + (m.idx ? m.idx[p] : p - uint32_t(m.recv_off[s]));
-}
-__global__ __launch_bounds__(256) void ordinals_kernel(OrdinalMap m, const uint32_t *__restrict__ pos, uint32_t n, unsigned long long *__restrict__ out) {
-	const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-	if (i < n) out[i] = pos[i] == 0xFFFFFFFFu ? ~0ull : to_global_ordinal(m, pos[i]);
-}
-
-// -u across shards: smallest global ordinal of every UMI over the shards' tables; then the table becomes a rank table
-__global__ __launch_bounds__(256) void min_rows_kernel(const unsigned long long *__restrict__ all, uint32_t rows, uint64_t n, unsigned long long *__restrict__ out) {
-	for (uint64_t i = uint64_t(blockIdx.x) * 256 + threadIdx.x; i < n; i += uint64_t(gridDim.x) * 256) {
-		unsigned long long m = ~0ull;
-		for (uint32_t r = 0; r < rows; ++r) { const unsigned long long v = all[uint64_t(r) * n + i]; m = v < m ? v : m; }
-		out[i] = m;
-	}
-}
-// rows of `len` bytes gathered by index: out[i] = in[idx[i]] (the quality strings follow the stable partition of their reads)
-__global__ __launch_bounds__(256) void gather_byte_rows_kernel(const uint8_t *__restrict__ in, const uint32_t *__restrict__ idx, uint32_t n, uint32_t len,
-                                                               uint8_t *__restrict__ out) {
-	for (uint64_t k = uint64_t(blockIdx.x) * 256 + threadIdx.x; k < uint64_t(n) * len; k += uint64_t(gridDim.x) * 256) {
-		const uint32_t i = uint32_t(k / len), b = uint32_t(k % len);
-		out[k] = in[uint64_t(idx[i]) * len + b];
-	}
-}
-// -M across shards: the UMI histograms of the shards added up
-__global__ __launch_bounds__(256) void sum_rows_kernel(const uint32_t *__restrict__ all, uint32_t rows, uint64_t n, uint32_t *__restrict__ out) {
-	for (uint64_t i = uint64_t(blockIdx.x) * 256 + threadIdx.x; i < n; i += uint64_t(gridDim.x) * 256) {
-		uint32_t sum = 0;
-		for (uint32_t r = 0; r < rows; ++r) sum += all[uint64_t(r) * n + i];
-		out[i] = sum;
-	}
-}
-__global__ __launch_bounds__(256) void ranks_to_table_kernel(const unsigned long long *__restrict__ sorted_ord, const uint32_t *__restrict__ code, uint32_t n,
-                                                             uint32_t *__restrict__ table) {
-	const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-	if (i < n) table[code[i]] = sorted_ord[i] == ~0ull ? 0xFFFFFFFFu : i;
-}
-
-}  // namespace dropest
+#include "transport.h"
+#include "k_shard.h"
 
 // CellsDataContainer::compare_cells (CellsDataContainer.cpp:329-344) on table rows: (requested_genes, requested_umis,
 // umis_number, barcode STRING) ascending.  Clean codes of one length order like their strings; anything else is decoded.
@@ -1196,13 +377,16 @@ void dropest_shard::partition_and_exchange() {
 			for (DevBuf<u64> *b : {&p_cb, &p_umi}) b->ensure(std::max<size_t>(n, 1));
 			for (DevBuf<u32> *b : {&p_gene, &p_aux}) b->ensure(std::max<size_t>(n, 1));
 		}
+		// the scatter writes the block this shard keeps straight to its place among the received ones, and counts the reads that do not fit
+		// the sampled widths
+		const int owner_bits = std::max(1, bit_length(uint64_t(world - 1)));
+		OwnerSelf self{};
+		if (any_sampled && packed) self.bad = reinterpret_cast<u32 *>(d_stats + 5);
+		self.owner = u32(rank);
+		self.w0 = x_w0.p + recv_off[size_t(rank)] - send_off[size_t(rank)];     // (index = position in the partition's output)
+		self.w1 = x_w1.p + recv_off[size_t(rank)] - send_off[size_t(rank)];
 		if (n) {
-			const int owner_bits = std::max(1, bit_length(uint64_t(world - 1)));
-			OwnerSelf self{};
-			if (any_sampled && packed) { HIP_CHECK(hipMemsetAsync(d_stats + 5, 0, 8, c.stream)); self.bad = reinterpret_cast<u32 *>(d_stats + 5); }
-			self.owner = u32(rank);
-			self.w0 = x_w0.p + recv_off[size_t(rank)] - send_off[size_t(rank)];     // (index = position in the partition's output)
-			self.w1 = x_w1.p + recv_off[size_t(rank)] - send_off[size_t(rank)];
+			if (self.bad) HIP_CHECK(hipMemsetAsync(d_stats + 5, 0, 8, c.stream));
 			if (packed && chunked_now) {
 				// (launched chunk by chunk below, each chunk's pieces leaving as soon as they are written)
 			} else if (packed) hipLaunchKernelGGL(owner_scatter_kernel<true>, dim3(nblocks), dim3(OP_T), 0, c.stream, r_cb, r_umi, r_gene, r_aux, n, u32(world), owner_bits, tpb, hist, digit_base,
@@ -1217,13 +401,6 @@ void dropest_shard::partition_and_exchange() {
 			if (!xchg_stream) HIP_CHECK(hipStreamCreateWithFlags(&xchg_stream, hipStreamNonBlocking));
 			while (ev_scat.size() < size_t(C_plan)) { hipEvent_t e; HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); ev_scat.push_back(e); }
 			while (ev_recv.size() < size_t(C_plan)) { hipEvent_t e; HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); ev_recv.push_back(e); }
-			const size_t WC = size_t(world) * size_t(C_plan);
-			const int owner_bits = std::max(1, bit_length(uint64_t(world - 1)));
-			OwnerSelf self{};
-			if (any_sampled) self.bad = reinterpret_cast<u32 *>(d_stats + 5);   // (cleared above)
-			self.owner = u32(rank);
-			self.w0 = x_w0.p + recv_off[size_t(rank)] - send_off[size_t(rank)];
-			self.w1 = x_w1.p + recv_off[size_t(rank)] - send_off[size_t(rank)];
 			std::vector<uint64_t> s_off(static_cast<size_t>(world)), s_cnt(static_cast<size_t>(world)), r_off(static_cast<size_t>(world)), r_cnt(static_cast<size_t>(world));
 			std::vector<uint64_t> s_run(send_off.begin(), send_off.begin() + world), r_run(recv_off.begin(), recv_off.begin() + world);
 			c.recv_chunks.clear();
@@ -1288,9 +465,8 @@ void dropest_shard::partition_and_exchange() {
 			tr->exchange(5, snd, rcv, elem, send_cnt.data(), recv_cnt.data(), c.stream);
 		}
 		auto &st = phases["all_to_all"];
-		uint64_t out = 0;
-		for (int p = 0; p < world; ++p) if (p != rank) out += send_cnt[size_t(p)];
-		st.bytes += double(out) * rec_bytes;   // bytes this shard put on the links (self block excluded)
+		const double out = double(send_off[size_t(world)] - send_cnt[size_t(rank)]);   // reads this shard put on the links (self block excluded)
+		st.bytes += out * rec_bytes;
 		phases["exchange_record_bytes"].bytes = double(rec_bytes);
 		if (r_have_qual && r_qlen) {   // the quality strings: gathered into the order of the partition, exchanged with the same counts
 			p_qual.ensure(std::max<size_t>(size_t(n) * r_qlen, 1)); x_qual.ensure(std::max<size_t>(size_t(n_recv) * r_qlen, 1));
@@ -1303,9 +479,7 @@ void dropest_shard::partition_and_exchange() {
 			void *rcv[1] = {x_qual.p};
 			const size_t elem[1] = {r_qlen};
 			tr->exchange(1, snd, rcv, elem, send_cnt.data(), recv_cnt.data(), c.stream);
-			uint64_t out_q = 0;
-			for (int p = 0; p < world; ++p) if (p != rank) out_q += send_cnt[size_t(p)];
-			st.bytes += double(out_q) * r_qlen;
+			st.bytes += out * r_qlen;
 			if (r_qual_var) {   // strings of several lengths: the length of every read's string travels the same way (1 byte per read)
 				p_qual_lens.ensure(std::max<size_t>(n, 1)); x_qual_lens.ensure(std::max<size_t>(n_recv, 1));
 				if (n) {
@@ -1317,7 +491,7 @@ void dropest_shard::partition_and_exchange() {
 				void *rcv1[1] = {x_qual_lens.p};
 				const size_t elem1[1] = {1};
 				tr->exchange(1, snd1, rcv1, elem1, send_cnt.data(), recv_cnt.data(), c.stream);
-				st.bytes += double(out_q);
+				st.bytes += out;
 			}
 		}
 		// The records stay packed: cb_sample, cb_insert, the sampled statistics and build_keys read them as they are (k_cbhash.h: ReadPack);
@@ -1762,6 +936,7 @@ void dropest_shard::merge_umi_distribution() {
 }
 
 #include "shard_merge_free.h"
+#include "shard_matrix.h"
 
 // 7. global view of the real cells: every shard's rows, all-gathered; first_global = the stream ordinal of the cell's first read
 void dropest_shard::build_global_table() {
@@ -1796,331 +971,6 @@ void dropest_shard::build_global_table() {
 	std::vector<size_t> cnt;
 	{ Phase p3(this, "cells:gather"); tr->gather_vec(mine, G, cnt); }
 	if (std::getenv("DROPEST_SHARD_TRACE")) fprintf(stderr, "[shard %d] real rows %zu of %zu, G %zu\n", rank, mine.size(), c.real.size(), G.size());
-}
-
-// 8. one matrix: global column order (identical on every shard), this shard's columns emitted on the device and written to
-// their places in the node-shared host buffer
-void dropest_shard::assemble_matrix(bool filtered_m) {
-	using namespace dropest;
-	dropest_ctx &c = *ctx;
-	const int slot = filtered_m ? 0 : 1;
-	Mat &M = mat[slot];
-	ctx->mat[slot].settle();   // (a straggler of the previous widening reads dec_begin / dec_end)
-	dropest::DevBuf<u64> &d_desc = d_desc_m[slot];
-	dropest::PinnedBuf<u64> &h_desc = h_desc_m[slot];
-	std::vector<u32> sel;
-	for (u32 i = 0; i < G.size(); ++i) if (!filtered_m || G[i].req_genes >= c.min_after) sel.push_back(i);
-	std::vector<u32> order;
-	{
-		Phase ph(this, filtered_m ? "order:cm" : "order:cm_raw");
-		order = order_rows(sel, !filtered_m);
-		if (filtered_m && c.cfg.max_cells > 0 && size_t(c.cfg.max_cells) < order.size())   // -C: the largest max_cells cells (CellsDataContainer.cpp:269-273)
-			order.erase(order.begin(), order.end() - c.cfg.max_cells);
-	}
-	Phase ph(this, filtered_m ? "matrix:cm" : "matrix:cm_raw");
-	const size_t ncols = order.size();
-	M.ncols = ncols; M.colptr.assign(ncols + 1, 0); M.col_barcode.resize(ncols);
-	std::vector<u32> &col_cell = M.col_cell, &col_start = M.col_start;   // (members: their copies to the device are not waited for here)
-	col_cell.clear(); col_start.clear();
-	std::vector<u64> desc;
-	uint64_t local_nnz = 0;
-	for (size_t j = 0; j < ncols; ++j) {
-		const GRow &r = G[order[j]];
-		const u32 len = filtered_m ? r.req_genes : r.n_genes;
-		M.col_barcode[j] = r.barcode;
-		M.colptr[j + 1] = M.colptr[j] + len;
-		if (int(r.rank) != rank) continue;
-		col_cell.push_back(r.local_id); col_start.push_back(u32(local_nnz));
-		desc.push_back(local_nnz); desc.push_back(M.colptr[j]); desc.push_back(len);
-		local_nnz += len;
-	}
-	M.dec_begin.clear(); M.dec_end.clear();
-	for (size_t k = 0; k < col_cell.size(); ++k) { M.dec_begin.push_back(u32(desc[3 * k + 1])); M.dec_end.push_back(u32(desc[3 * k + 1] + desc[3 * k + 2])); }
-	M.nnz = M.colptr[ncols];
-	if (M.nnz > 0xFFFFFFF0ull || local_nnz > 0xFFFFFFF0ull) throw UnsupportedError("count matrix with more than 2^32 non-zeros");
-	M.colptr_p = M.colptr.data(); M.barcode_p = M.col_barcode.data();
-	M.colptr32.resize(ncols + 1);
-	for (size_t j = 0; j <= ncols; ++j) M.colptr32[j] = u32(M.colptr[j]);
-	M.colptr32_p = M.colptr32.data();
-	SharedLayout L;
-	{ Phase p2(this, filtered_m ? "cm:open_shared" : "raw:open_shared"); L = open_shared(M, slot, 0); }
-	const u32 nc = u32(col_cell.size());
-	if (nc && local_nnz) {
-		if (!L.slots) c.emit_columns_device(filtered_m, false, col_cell, col_start, local_nnz, false);   // (a slots step emits the byte form of the local matrix: place_columns)
-		// (the same matrix assembled again inside one step -- the overflow fall-back -- or in the next step: the previous copy has left the
-		// staging buffer by then in every run seen, but nothing said so: wait, it costs nothing on a drained stream)
-		if (desc_in_flight[slot]) HIP_CHECK(stream_wait(c.stream));
-		d_desc.ensure(desc.size()); h_desc.ensure(desc.size());
-		std::memcpy(h_desc.p, desc.data(), desc.size() * 8);
-		HIP_CHECK(hipMemcpyAsync(d_desc.p, h_desc.p, desc.size() * 8, hipMemcpyHostToDevice, c.stream));
-		desc_in_flight[slot] = true;
-	}
-	Phase p3(this, filtered_m ? "cm:place" : "raw:place");
-	place_columns(M, slot, filtered_m, L, d_desc.p, nc, local_nnz, nullptr, col_start.data());
-}
-
-// The node-shared host buffer of one matrix (collective: every shard takes the same decisions -- the gene ids are the agreed ones).
-// [head_bytes of the caller][payload][byte form: one segment per shard].  Payload: 32-bit rows | values; 16-bit rows | values; byte form:
-// deltas | values (each padded to 16 bytes).  A segment = 4 words (rows listed, values listed, 0, 0) + 4 arrays of list_cap words (row
-// positions, rows, value positions, values); list_cap comes from the GLOBAL nnz: the same on every shard.
-dropest_shard::SharedLayout dropest_shard::open_shared(Mat &M, int slot, size_t head_bytes) {
-	using namespace dropest;
-	dropest_ctx &c = *ctx;
-	SharedLayout L{};
-	L.bytes = byte_matrix && !wide_now[slot];
-	L.narrow = !L.bytes && narrow_matrix && c.narrow_possible();
-	L.base = (head_bytes + 15) & ~size_t(15);
-	L.list_cap = u32(std::min<uint64_t>(byte_list_cap ? byte_list_cap : (1u << 20), (M.nnz + 15) & ~15ull));
-	L.off_val = (size_t(M.nnz) + 15) & ~size_t(15); L.off_seg = 2 * L.off_val; L.seg_bytes = 16 + 16 * size_t(L.list_cap);
-	// slots step: the buffer holds the 32-bit slots only -- rows | values, each padded to whole 64-byte lines (the widening stores whole
-	// lines); every shard's bytes cross its link as the byte form of its LOCAL matrix and never stand in the shared buffer
-	L.slots = L.bytes && slots_matrix;
-	if (L.slots) L.bytes = false;
-	L.off_slots = (L.base + 63) & ~size_t(63);   // (from the buffer's start: that is page-aligned)
-	L.slots_stride = ((size_t(M.nnz) + 15) & ~size_t(15)) * 4;
-	const size_t payload = L.slots ? L.off_slots - L.base + std::max<size_t>(2 * L.slots_stride, 64)   // (an empty matrix still gets a buffer: the transports map what they are asked for)
-	                               : (L.bytes ? L.off_seg + L.seg_bytes * size_t(world) : std::max<size_t>(size_t(M.nnz), 1) * (L.narrow ? 4 : 8));
-	ctx->mat[slot].settle();   // (a straggler of the previous step's widening may still be leaving: the buffer is about to be rewritten or replaced)
-	L.host = static_cast<char *>(tr->shared_host(slot, L.base + payload, &L.dev));
-	char *host = L.host + L.base;
-	M.narrow = L.narrow; M.widened = false; M.ovf_pos.clear(); M.ovf_val.clear();
-	M.bytes = L.bytes; M.lists_ready = false;
-	M.rows = M.vals = nullptr; M.rows16 = M.vals16 = nullptr; M.delta8 = M.vals8 = nullptr;
-	M.slots = L.slots; M.slot_rows = M.slot_vals = nullptr; M.shipped = false; M.encoded = false;
-	if (L.slots) {
-		M.slot_rows = reinterpret_cast<u32 *>(L.host + L.off_slots); M.slot_vals = reinterpret_cast<u32 *>(L.host + L.off_slots + L.slots_stride);
-		M.d_slot_rows = reinterpret_cast<u32 *>(static_cast<char *>(L.dev) + L.off_slots); M.d_slot_vals = reinterpret_cast<u32 *>(static_cast<char *>(L.dev) + L.off_slots + L.slots_stride);
-		M.rows = M.slot_rows; M.vals = M.slot_vals;
-		return L;
-	}
-	if (L.bytes) {
-		M.delta8 = reinterpret_cast<const uint8_t *>(host); M.vals8 = reinterpret_cast<const uint8_t *>(host) + L.off_val;
-		M.segments = host + L.off_seg; M.seg_bytes = L.seg_bytes; M.list_cap = L.list_cap;
-	} else if (L.narrow) { M.rows16 = reinterpret_cast<const uint16_t *>(host); M.vals16 = reinterpret_cast<const uint16_t *>(host) + M.nnz; }
-	else { M.rows = reinterpret_cast<const u32 *>(host); M.vals = reinterpret_cast<const u32 *>(host) + M.nnz; }
-	return L;
-}
-
-// this shard's columns (emitted into c.mat[slot] on the device; d_descr: local offset, global offset, length of each) -> their global
-// places in the shared buffer, in the form open_shared chose
-void dropest_shard::place_columns(Mat &M, int slot, bool filtered_m, const SharedLayout &L, const unsigned long long *d_descr, dropest::u32 nc, uint64_t local_nnz, hipStream_t st,
-                                  const dropest::u32 *local_start) {
-	using namespace dropest;
-	dropest_ctx &c = *ctx;
-	if (!st) st = c.stream;
-	char *d_payload = static_cast<char *>(L.dev) + L.base;
-	const dropest_ctx::MatrixResult &R = c.mat[slot];
-	const bool work = nc && local_nnz;
-	if (L.slots) {
-		// The columns leave as the byte form of this shard's LOCAL matrix (the emit and the chunked copies of one context: whole lines at the
-		// link's streaming rate, whatever the columns' lengths -- placing bytes at their GLOBAL places straight from a kernel met ragged column
-		// ends with byte stores over PCIe: 22 GB/s on cm_raw's short columns), and the pool's host threads widen every chunk of columns into the
-		// shared 32-bit slots at the columns' global places as soon as its arrival flag is up (matrix_decode.h).
-		M.d_descr = d_descr; M.nc = nc; M.local_nnz = local_nnz;
-		if (!work) return;
-		dropest_ctx::WireTarget T;
-		T.rows = M.slot_rows; T.vals = M.slot_vals; T.global_nnz = M.nnz; T.d_descr = d_descr;
-		T.begin = M.dec_begin.empty() ? M.h_begin.p : M.dec_begin.data();
-		T.end = M.dec_end.empty() ? M.h_end.p : M.dec_end.data();
-		const std::vector<u32> &cells = filtered_m ? M.col_cell : raw_plan.col_cell, &starts = filtered_m ? M.col_start : raw_plan.col_start;
-		c.ship_columns_to_slots(filtered_m, false, cells, starts, local_nnz, T, st);
-		M.shipped = true;
-		return;
-	}
-	if (L.bytes) {
-		u32 *seg_words = reinterpret_cast<u32 *>(d_payload + L.off_seg + L.seg_bytes * size_t(rank));
-		d_list_count.ensure(8);
-		u32 *cnt = d_list_count.p + 4 * slot;
-		HIP_CHECK(hipMemsetAsync(cnt, 0, 16, st));
-		if (work) {
-			u32 *lists = seg_words + 4;
-			const size_t cap = L.list_cap;
-			{
-			auto launch = [&] {
-				hipLaunchKernelGGL(place_columns_bytes_kernel, dim3(nc), dim3(filtered_m ? 256 : 64), 0, st, d_descr, R.d_row.p, R.d_val.p,
-				                   reinterpret_cast<uint8_t *>(d_payload), reinterpret_cast<uint8_t *>(d_payload) + L.off_val, cnt,
-				                   lists, lists + cap, lists + 2 * cap, lists + 3 * cap, L.list_cap);
-			};
-			if (st == c.stream) c.timed(filtered_m ? "place_columns:cm" : "place_columns:cm_raw", double(local_nnz) * 10, launch);
-			else launch();   // (the context's launch timer brackets its own stream)
-			}
-		}
-		hipLaunchKernelGGL(copy_words_kernel, dim3(1), dim3(64), 0, st, cnt, seg_words, 4u);   // the counts, behind the lists on the stream
-		HIP_CHECK(hipGetLastError());
-		return;
-	}
-	constexpr u32 OVF_CAP = 1u << 16;
-	if (work) {
-		if (L.narrow) {
-			d_ovf.ensure(1 + 3 * size_t(OVF_CAP));
-			HIP_CHECK(hipMemsetAsync(d_ovf.p, 0, 4, c.stream));
-			hipLaunchKernelGGL(place_columns_narrow_kernel, dim3(nc), dim3(256), 0, c.stream, d_descr, R.d_row.p, R.d_val.p,
-			                   reinterpret_cast<uint16_t *>(d_payload), reinterpret_cast<uint16_t *>(d_payload) + M.nnz, d_ovf.p, OVF_CAP);
-		} else
-			hipLaunchKernelGGL(place_columns_kernel, dim3(nc), dim3(256), 0, c.stream, d_descr, R.d_row.p, R.d_val.p,
-			                   reinterpret_cast<u32 *>(d_payload), reinterpret_cast<u32 *>(d_payload) + M.nnz);
-		HIP_CHECK(hipGetLastError());
-	}
-	if (L.narrow) {   // the (rare) entries beyond 16 bits of every shard, gathered on the host
-		struct Ovf { u64 pos; u32 val, pad; };
-		std::vector<Ovf> mine, all;
-		if (work) {
-			u32 count = 0;
-			c.fetch(&count, d_ovf.p, 4);
-			if (count > OVF_CAP) throw UnsupportedError("more than 2^16 matrix entries beyond 65534 on one shard: set the shard option narrow_matrix to 0");
-			if (count) {
-				std::vector<u32> raw(3 * size_t(count));
-				c.fetch(raw.data(), d_ovf.p + 1, raw.size() * 4);
-				for (u32 i = 0; i < count; ++i) mine.push_back(Ovf{u64(raw[3 * i]) | (u64(raw[3 * i + 1]) << 32), raw[3 * i + 2], 0});
-			}
-		}
-		std::vector<size_t> cnt;
-		tr->gather_vec(mine, all, cnt);
-		std::sort(all.begin(), all.end(), [](const Ovf &a, const Ovf &b) { return a.pos < b.pos; });
-		for (const Ovf &o : all) { M.ovf_pos.push_back(o.pos); M.ovf_val.push_back(o.val); }
-	}
-}
-
-// cm_raw without a host table of all the real cells.  Its columns are the real cells of ALL shards in the order of ONE container's cell
-// ids = the stream ordinal of every cell's first read; on a shard the real cells stand in that order already (local ids are first-seen
-// ranks, and the blocks a shard received stand in stream order).  So the global matrix is a merge of `world` ascending lists:
-//   plan_raw           (host) this shard's columns, their nnz prefix; ONE small collective: columns, nnz and ordinal queries per shard
-//   assemble_raw_device        first-read ordinals on the device (the positions did not travel with a packed exchange: two small
-//                              device all-to-alls ask the sources), all-gather of (ordinal, nnz prefix) of every shard's columns --
-//                              16 bytes per column over the links --, then one thread per local column: binary searches in the other
-//                              shards' lists give its global place and nnz offset; it writes colptr / barcode of its column into
-//                              the shared buffer and the descriptor the placing kernel reads.
-// The host table (build_global_table) then holds the filtered candidates only.  Falls back to the host plan when a shard's cells are
-// not in ordinal order (never seen: a guard) or the option raw_on_device is off.
-bool dropest_shard::plan_raw() {
-	using namespace dropest;
-	dropest_ctx &c = *ctx;
-	Phase ph(this, "raw:plan");
-	RawPlan &P = raw_plan;
-	P.col_cell.clear(); P.col_start.clear(); P.query.clear(); P.pre.assign(1, 0);
-	const bool ask = exchanged && !idx_exchanged;
-	P.q_out.assign(size_t(world), 0);
-	uint64_t ok = raw_on_device ? 1 : 0;
-	u32 last = 0, src = 0;
-	for (const HostCell &h : c.real) {
-		if (h.merged || h.excluded || h.row.n_genes < c.min_before) continue;
-		const u32 pos = h.row.first_read;
-		if (pos == 0xFFFFFFFFu || (!P.col_cell.empty() && pos <= last)) { ok = 0; break; }
-		last = pos;
-		if (P.pre.back() + h.row.n_genes > 0xFFFFFFF0ull) throw UnsupportedError("count matrix with more than 2^32 non-zeros");
-		P.col_cell.push_back(h.id); P.col_start.push_back(u32(P.pre.back())); P.pre.push_back(P.pre.back() + h.row.n_genes);
-		if (ask) {
-			while (src + 1 < u32(world) && pos >= recv_off[size_t(src) + 1]) ++src;
-			P.query.push_back(u32(pos - recv_off[src])); ++P.q_out[src];
-		} else
-			P.query.push_back(pos);
-	}
-	// [ok, columns, nnz, queries to shard 0 .. world-1] of every shard
-	const size_t w = 3 + size_t(world);
-	std::vector<uint64_t> mine(w, 0);
-	mine[0] = ok; mine[1] = P.col_cell.size(); mine[2] = P.pre.back();
-	for (int p = 0; p < world; ++p) mine[3 + size_t(p)] = P.q_out[size_t(p)];
-	P.counts.assign(w * size_t(world), 0);
-	tr->gather_host(mine.data(), w * 8, P.counts.data());
-	P.ncols = P.nnz = 0;
-	P.q_in.assign(size_t(world), 0);
-	for (int p = 0; p < world; ++p) {
-		const uint64_t *row = P.counts.data() + w * size_t(p);
-		ok &= row[0]; P.ncols += row[1]; P.nnz += row[2]; P.q_in[size_t(p)] = row[3 + size_t(rank)];
-	}
-	if (P.nnz > 0xFFFFFFF0ull) throw UnsupportedError("count matrix with more than 2^32 non-zeros");
-	return ok != 0;
-}
-
-void dropest_shard::assemble_raw_device() {
-	using namespace dropest;
-	dropest_ctx &c = *ctx;
-	Phase ph(this, "matrix:cm_raw");
-	RawPlan &P = raw_plan;
-	Mat &M = mat[1];
-	ctx->mat[1].settle();
-	const size_t w = 3 + size_t(world);
-	const u32 nl = u32(P.col_cell.size());
-	const uint64_t ncols = P.ncols;
-	M.ncols = ncols; M.nnz = P.nnz; M.colptr.clear(); M.col_barcode.clear(); M.colptr32.clear();
-	// head of the shared buffer: colptr64[ncols + 1] | colptr32[ncols + 1] | barcodes[ncols]
-	const size_t off_c32 = (ncols + 1) * 8, off_bc = (off_c32 + (ncols + 1) * 4 + 15) & ~size_t(15), head = off_bc + ncols * 8;
-	const SharedLayout L = open_shared(M, 1, head);
-	M.colptr_p = reinterpret_cast<const u64 *>(L.host); M.colptr32_p = reinterpret_cast<const u32 *>(L.host + off_c32);
-	M.barcode_p = reinterpret_cast<const u64 *>(L.host + off_bc);
-	if (rank == 0) {   // the closing entry is nobody's column
-		reinterpret_cast<u64 *>(L.host)[ncols] = P.nnz;
-		reinterpret_cast<u32 *>(L.host + off_c32)[ncols] = u32(P.nnz);
-	}
-	// this shard's (first-read ordinal [nl] | nnz prefix [nl + 1])
-	d_plan_mine.ensure(2 * size_t(nl) + 1); d_q.ensure(std::max<u32>(nl, 1)); d_col_cell.ensure(std::max<u32>(nl, 1));
-	h_plan.ensure(size_t(nl) + 1 + size_t(nl));   // staging of its own (cm's descriptors may still be on their way from their staging buffer): prefix (u64) | queries, cells (u32)
-	std::memcpy(h_plan.p, P.pre.data(), (size_t(nl) + 1) * 8);
-	u32 *h32 = reinterpret_cast<u32 *>(h_plan.p + nl + 1);
-	if (nl) { std::memcpy(h32, P.query.data(), size_t(nl) * 4); std::memcpy(h32 + nl, P.col_cell.data(), size_t(nl) * 4); }
-	HIP_CHECK(hipMemcpyAsync(d_plan_mine.p + nl, h_plan.p, (size_t(nl) + 1) * 8, hipMemcpyHostToDevice, c.stream));
-	if (nl) {
-		HIP_CHECK(hipMemcpyAsync(d_q.p, h32, size_t(nl) * 4, hipMemcpyHostToDevice, c.stream));
-		HIP_CHECK(hipMemcpyAsync(d_col_cell.p, h32 + nl, size_t(nl) * 4, hipMemcpyHostToDevice, c.stream));
-	}
-	if (exchanged && !idx_exchanged) {
-		QueryTable t{};
-		t.world = u32(world);
-		uint64_t n_in = 0;
-		for (int p = 0; p < world; ++p) {
-			t.in_off[p] = n_in; n_in += P.q_in[size_t(p)]; t.part_off[p] = send_off[size_t(p)]; t.first_ord[p] = first_ord[size_t(p)];
-			t.out_off[p + 1] = t.out_off[p] + P.q_out[size_t(p)];
-		}
-		t.in_off[world] = n_in;
-		d_q_in.ensure(std::max<uint64_t>(n_in, 1)); d_q_ans.ensure(std::max<uint64_t>(n_in, 1)); d_q_back.ensure(std::max<u32>(nl, 1));
-		{ const void *snd[1] = {d_q.p}; void *rcv[1] = {d_q_in.p}; const size_t elem[1] = {4};
-		  tr->exchange(1, snd, rcv, elem, P.q_out.data(), P.q_in.data(), c.stream); }
-		if (n_in) {
-			hipLaunchKernelGGL(answer_queries_kernel, dim3(u32((n_in + 255) / 256)), dim3(256), 0, c.stream, t, d_q_in.p, u32(n_in), p_idx.p, d_q_ans.p);
-			HIP_CHECK(hipGetLastError());
-		}
-		{ const void *snd[1] = {d_q_ans.p}; void *rcv[1] = {d_q_back.p}; const size_t elem[1] = {4};
-		  tr->exchange(1, snd, rcv, elem, P.q_in.data(), P.q_out.data(), c.stream); }
-		if (nl) hipLaunchKernelGGL(ordinals_from_answers_kernel, dim3((nl + 255) / 256), dim3(256), 0, c.stream, t, d_q_back.p, nl, reinterpret_cast<unsigned long long *>(d_plan_mine.p));
-	} else if (nl)
-		hipLaunchKernelGGL(ordinals_kernel, dim3((nl + 255) / 256), dim3(256), 0, c.stream, ordinal_map(), d_q.p, nl, reinterpret_cast<unsigned long long *>(d_plan_mine.p));
-	HIP_CHECK(hipGetLastError());
-	// every shard's block to every shard
-	RawPlanTable pt{};
-	pt.world = u32(world); pt.rank = u32(rank);
-	std::vector<size_t> off(static_cast<size_t>(world), 0), bytes(static_cast<size_t>(world), 0);
-	size_t total = 0;
-	for (int p = 0; p < world; ++p) {
-		const uint64_t n_p = P.counts[w * size_t(p) + 1];
-		pt.off[p] = total; pt.n[p] = u32(n_p);
-		off[size_t(p)] = total * 8; bytes[size_t(p)] = (2 * size_t(n_p) + 1) * 8;
-		total += 2 * size_t(n_p) + 1;
-	}
-	d_plan_all.ensure(total);
-	tr->gather_dev(d_plan_mine.p, d_plan_all.p, off.data(), bytes.data(), c.stream);
-	d_desc_raw.ensure(std::max<size_t>(3 * size_t(nl), 1));
-	M.dec_begin.clear(); M.dec_end.clear();
-	if (L.slots) { M.h_begin.ensure(std::max<u32>(nl, 1)); M.h_end.ensure(std::max<u32>(nl, 1)); }
-	if (nl) {
-		char *d_head = static_cast<char *>(L.dev);
-		hipLaunchKernelGGL(plan_raw_columns_kernel, dim3((nl + 255) / 256), dim3(256), 0, c.stream, pt, reinterpret_cast<const unsigned long long *>(d_plan_all.p),
-		                   d_col_cell.p, reinterpret_cast<const unsigned long long *>(c.cell_cb.p), nl, reinterpret_cast<unsigned long long *>(d_desc_raw.p),
-		                   reinterpret_cast<unsigned long long *>(d_head), reinterpret_cast<uint32_t *>(d_head + off_c32),
-		                   reinterpret_cast<unsigned long long *>(d_head + off_bc), L.slots ? M.h_begin.p : static_cast<u32 *>(nullptr),
-		                   L.slots ? M.h_end.p : static_cast<u32 *>(nullptr));
-		HIP_CHECK(hipGetLastError());
-	}
-	const uint64_t local_nnz = P.pre.back();
-	if (nl && local_nnz && !L.slots) c.emit_columns_device(false, false, P.col_cell, P.col_start, local_nnz, false);
-	// the placing kernel on its own stream (byte form: nothing on the host waits for it before the end of the step)
-	hipStream_t st = c.stream;
-	if ((L.bytes || L.slots) && !getenv("DROPEST_SHARD_NO_PLACE_STREAM")) {
-		if (!place_stream) { HIP_CHECK(hipStreamCreateWithFlags(&place_stream, hipStreamNonBlocking)); HIP_CHECK(hipEventCreateWithFlags(&ev_place, hipEventDisableTiming)); }
-		HIP_CHECK(hipEventRecord(ev_place, c.stream));
-		HIP_CHECK(hipStreamWaitEvent(place_stream, ev_place, 0));
-		st = place_stream;
-	}
-	place_columns(M, 1, false, L, reinterpret_cast<const unsigned long long *>(d_desc_raw.p), nl, local_nnz, st, P.col_start.data());
 }
 
 void dropest_shard::step() {
@@ -2242,76 +1092,6 @@ void dropest_shard::step() {
 		Phase ph(this, "matrix:lists"); for (int k = 0; k < 2; ++k) collect_lists(mat[k]);   // (a slots step has no byte form in the buffer: nothing to collect)
 	}
 	c.collect_timings();
-}
-
-void dropest_shard::finish_slots(int slot) {
-	using namespace dropest;
-	Mat &M = mat[slot];
-	if (!M.slots || !M.shipped) return;
-	M.shipped = false;
-	dropest_ctx &c = *ctx;
-	if (c.wire_finish(c.mat[slot])) return;
-	// The lists of this shard's byte form overflowed (very sparse columns: a small cell lists nearly every row).  The slots ARE the 32-bit
-	// form: this shard emits its columns as 32-bit arrays and places them there directly -- its own decision, no collective (ADVICE r3:
-	// the step cannot fail for the shape of the data).
-	phases["matrix:overflow"].launches++;
-	const bool filtered_m = slot == 0;
-	c.emit_columns_device(filtered_m, false, filtered_m ? M.col_cell : raw_plan.col_cell, filtered_m ? M.col_start : raw_plan.col_start, M.local_nnz, false);
-	const dropest_ctx::MatrixResult &R = c.mat[slot];
-	hipLaunchKernelGGL(place_columns_kernel, dim3(M.nc), dim3(256), 0, c.stream, M.d_descr, R.d_row.p, R.d_val.p, M.d_slot_rows, M.d_slot_vals);
-	HIP_CHECK(hipGetLastError());
-	HIP_CHECK(stream_wait(c.stream));
-}
-
-// The byte form of a matrix whose step ended with the slots (dropest_shard_matrix_bytes asks for it): encoded from the slots, once.
-void dropest_shard::encode_bytes(Mat &M) {
-	using namespace dropest;
-	if (M.encoded) return;
-	M.enc_delta.assign(size_t(M.nnz), 0); M.enc_vals.assign(size_t(M.nnz), 0);
-	M.rl_pos.clear(); M.rl_row.clear(); M.vl_pos.clear(); M.vl_val.clear();
-	const u32 *cp = M.colptr32_p;
-	for (uint64_t c = 0; c < M.ncols; ++c) {
-		uint32_t prev1 = 0;
-		for (uint32_t k = cp[c]; k < cp[c + 1]; ++k) {
-			const uint32_t row = M.slot_rows[k], v = M.slot_vals[k], d = row + 1u - prev1;
-			prev1 = row + 1u;
-			M.enc_delta[k] = uint8_t(d >= 255u ? 255u : d); M.enc_vals[k] = uint8_t(v >= 255u ? 255u : v);
-			if (d >= 255u) { M.rl_pos.push_back(k); M.rl_row.push_back(row); }
-			if (v >= 255u) { M.vl_pos.push_back(k); M.vl_val.push_back(v); }
-		}
-	}
-	M.delta8 = M.enc_delta.data(); M.vals8 = M.enc_vals.data(); M.lists_ready = true; M.encoded = true;
-}
-
-// the byte form's lists: every shard's segment of the shared buffer (written through its PCIe link, complete after the barrier)
-// -> one list of a kind (a matrix whose lists overflowed on some shard was placed again without the byte form before this: step())
-bool dropest_shard::lists_overflowed(const Mat &M) const {
-	if (!M.bytes) return false;
-	for (int p = 0; p < world; ++p) {
-		const u32 *w = reinterpret_cast<const u32 *>(M.segments + M.seg_bytes * size_t(p));
-		if (w[0] > M.list_cap || w[1] > M.list_cap) return true;
-	}
-	return false;
-}
-
-void dropest_shard::collect_lists(Mat &M) {
-	using namespace dropest;
-	if (!M.bytes || M.lists_ready) return;
-	size_t nr = 0, nv = 0;
-	for (int p = 0; p < world; ++p) {
-		const u32 *w = reinterpret_cast<const u32 *>(M.segments + M.seg_bytes * size_t(p));
-		if (w[0] > M.list_cap || w[1] > M.list_cap) throw InvalidError("internal: a byte-form matrix kept overflowed lists");
-		nr += w[0]; nv += w[1];
-	}
-	M.rl_pos.resize(nr); M.rl_row.resize(nr); M.vl_pos.resize(nv); M.vl_val.resize(nv);
-	size_t ar = 0, av = 0;
-	for (int p = 0; p < world; ++p) {
-		const u32 *w = reinterpret_cast<const u32 *>(M.segments + M.seg_bytes * size_t(p));
-		const u32 *l = w + 4;
-		if (w[0]) { std::memcpy(M.rl_pos.data() + ar, l, size_t(w[0]) * 4); std::memcpy(M.rl_row.data() + ar, l + M.list_cap, size_t(w[0]) * 4); ar += w[0]; }
-		if (w[1]) { std::memcpy(M.vl_pos.data() + av, l + 2 * size_t(M.list_cap), size_t(w[1]) * 4); std::memcpy(M.vl_val.data() + av, l + 3 * size_t(M.list_cap), size_t(w[1]) * 4); av += w[1]; }
-	}
-	M.lists_ready = true;
 }
 
 // N-UMI merge across shards (umi_merge_host.h): global first occurrences of the tie candidates, offsets into the ONE rand()
@@ -2717,24 +1497,6 @@ dropest_status dropest_shard_merged_barcodes(dropest_shard *s, uint64_t *n, uint
 	});
 }
 
-// test hook (tests/test_host_mailbox.py: processes on the CPU): `rounds` gathers of `bytes` patterned bytes per rank, every one checked;
-// returns 0, or the round (1-based) in which a slot did not hold what its rank wrote
-int dropest_test_host_mailbox(uint64_t token, int32_t rank, int32_t world, uint32_t rounds, uint64_t bytes) {
-	try {
-		dropest::HostMailbox mb(token, rank, world);
-		std::vector<unsigned char> mine(bytes), all(size_t(bytes) * size_t(world));
-		for (uint32_t r = 0; r < rounds; ++r) {
-			const size_t n = r % 3 == 2 ? size_t(bytes) / 2 : size_t(bytes);          // sizes change between rounds (the same on every rank)
-			for (size_t i = 0; i < n; ++i) mine[i] = (unsigned char)(rank * 131 + r * 7 + i * 13);
-			mb.gather(mine.data(), n, all.data());
-			for (int p = 0; p < world; ++p)
-				for (size_t i = 0; i < n; ++i) if (all[size_t(p) * n + i] != (unsigned char)(p * 131 + r * 7 + i * 13)) return int(r + 1);
-		}
-		mb.barrier();
-		return 0;
-	} catch (const std::exception &e) { g_last_error = e.what(); return -1; }
-}
-
 dropest_status dropest_shard_phase_stats(dropest_shard *s, uint32_t *n, dropest_kernel_stat *out) {
 	return guarded([&] {
 		if (!s || !n) throw InvalidError("null argument");
@@ -2796,3 +1558,5 @@ dropest_status dropest_shard_set_option(dropest_shard *s, const char *key, int64
 }
 
 }  // extern "C"
+
+#include "transport_test.h"

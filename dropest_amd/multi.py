@@ -1,4 +1,4 @@
-"""Sharded runs over several MI355X: ctypes binding of the C++ runner (csrc/shard_run.h, dropest_shard_* in
+"""Sharded runs over several MI355X: ctypes binding of the C++ runner (csrc/shard_run.h with transport.h / shard_matrix.h / k_shard.h, dropest_shard_* in
 include/dropest_amd.h).  All orchestration -- partition by owner, the RCCL all-to-all, key-field agreement, the whitelist
 CB merge across shards, N-UMI resolution against the one global rand() sequence, global column order, every shard writing
 its columns into node-shared host memory -- is in the library; this module only creates the shards and hands out views.

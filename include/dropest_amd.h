@@ -659,6 +659,11 @@ dropest_status dropest_shard_phase_stats(dropest_shard *shard, uint32_t *n, drop
  * one shard: measures what a second shard would add), "reset_phase_stats", "byte_matrix" / "narrow_matrix" (the form the step writes
  * the matrices in: bytes by default, else 16-bit when every gene id fits, else 32-bit), "packed_exchange" */
 dropest_status dropest_shard_set_option(dropest_shard *shard, const char *key, int64_t value);
+/* Test hook: the all-to-all(v) and the device gather of a shard transport on small patterned arrays.  plane 0: `world` threads over an
+ * in-process group on `device`; plane 1: this process is rank `rank` of `world` (id from dropest_shard_unique_id, as for
+ * dropest_shard_create).  in_place: bit a set = array a's own block is left where it is.  0, the number of the first failed check, or -1
+ * (dropest_last_error). */
+int dropest_test_transport(int plane, int32_t rank, int32_t world, const uint8_t id[128], int device, uint32_t in_place);
 
 /* Sort keys wider than 64 bits.  The reference's containers have no such limit (StringIndexer.cpp:10-18: ids are size_t); one
  * context packs cell id | gene | UMI into one 64-bit sort key and dropest_set_initialized fails with DROPEST_ERR_UNSUPPORTED

@@ -1,6 +1,6 @@
 """The sharded runner with one PROCESS per shard (what bench.py launches under torch.distributed.run), on a box with one GPU: the
 processes share the device, so the device data of the collectives crosses through POSIX shared memory (DROPEST_SHARD_DATAPLANE=shm,
-csrc/shard_run.h) instead of RCCL, which refuses two ranks on one device.  Everything else is the multi-process code of a real run: the
+csrc/transport.h) instead of RCCL, which refuses two ranks on one device.  Everything else is the multi-process code of a real run: the
 host collectives through the shm mailbox with real peers, the node-shared result buffers registered in every process, the step's sequence
 of collectives -- partition, all-to-all(v), key-field agreement, the sharded whitelist merge, N-UMI resolution, device-planned cm_raw,
 every shard writing its columns.  Results must equal ONE context over the whole stream."""

@@ -1,4 +1,4 @@
-"""HostMailbox (csrc/shard_run.h): the host collectives of a multi-process run -- one POSIX shm object, a slot per rank in two halves used
+"""HostMailbox (csrc/transport.h; the hook: csrc/transport_test.h): the host collectives of a multi-process run -- one POSIX shm object, a slot per rank in two halves used
 in turn, one sense-reversing barrier per gather.  Real processes on the CPU (the RCCL transport itself needs one GPU per process)."""
 import ctypes as C
 import multiprocessing as mp
