@@ -217,6 +217,9 @@ def lib():
         "dropest_deal_range": (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_int32, vp, P(C.c_uint32)]),
         "dropest_reserve_reads": (C.c_int, [vp, C.c_uint64]),
         "dropest_shard_group_step": (C.c_int, [vp, C.c_int32]),
+        "dropest_shard_merge_validation_samples": (C.c_int, [vp, P(ValidationOpts), P(ValidationSample), C.c_uint32]),
+        "dropest_shard_group_merge_validation_samples": (C.c_int, [vp, C.c_int32, P(ValidationOpts), P(ValidationSample), C.c_uint32]),
+        "dropest_validation_cut_pairs": (C.c_int, [vp, C.c_uint64, C.c_int32, vp]),
         "dropest_shard_matrix": (C.c_int, [vp, C.c_int, u64p, u64p, P(vp), P(vp), P(vp), P(vp)]),
         "dropest_shard_matrix_form": (C.c_int, [vp, C.c_int, P(C.c_int32)]),
         "dropest_shard_matrix_narrow": (C.c_int, [vp, C.c_int, u64p, u64p, P(vp), P(vp), P(vp), P(vp), u64p, P(vp), P(vp)]),
@@ -247,6 +250,7 @@ EXPORTED_SYMBOLS = [
     "dropest_real_candidate_rows", "dropest_dev_copy_device", "dropest_umi_distribution",
     "dropest_collisions_adjusted_sizes", "dropest_poisson_intersection_prob", "dropest_poisson_upper_tail",
     "dropest_merge_validation", "dropest_merge_validation_samples",
+    "dropest_shard_merge_validation_samples", "dropest_shard_group_merge_validation_samples", "dropest_validation_cut_pairs",
     "dropest_set_umi_qualities", "dropest_umi_quality_length", "dropest_cell_molecule_qualities",
     "dropest_set_umi_qualities_var", "dropest_cell_molecule_quality_lengths",
     "dropest_exclude_cell", "dropest_merge_cells", "dropest_merge_umis",
@@ -825,6 +829,48 @@ def deal_range(first_ordinal, n, quota, n_shards):
     if rc != 0:
         raise DropestError(rc, lib().dropest_last_error().decode())
     return [(int(out[3 * i]), int(out[3 * i + 1]), int(out[3 * i + 2])) for i in range(k.value)]
+
+
+def validation_cut_pairs(cnt, world):
+    """bounds[world + 1]: shard r of a sharded merge validation evaluates pairs [bounds[r], bounds[r + 1]) of a sample whose pair p has
+    cnt[p] common genes (dropest_validation_cut_pairs; host logic, no GPU)."""
+    cnt = np.ascontiguousarray(cnt, np.uint32)
+    bounds = np.zeros(int(world) + 1, np.uint64)
+    rc = lib().dropest_validation_cut_pairs(cnt.ctypes.data, len(cnt), int(world), bounds.ctypes.data)
+    if rc != 0:
+        raise DropestError(rc, lib().dropest_last_error().decode())
+    return [int(x) for x in bounds]
+
+
+VALIDATION_KINDS = (("cell1", np.uint64), ("cell2", np.uint64), ("umis1", np.uint32), ("umis2", np.uint32), ("edit_distance", np.uint32),
+                    ("intersection", np.uint32), ("expected", np.float64), ("probability", np.float64))
+
+
+def validation_request(samples, max_draws=0, round_candidates=0, max_keys_per_chunk=0):
+    """(samples as a tuple of (min_ed, max_ed, n_pairs), single?, ValidationOpts, ValidationSample array, the output arrays it points to)
+    for the calls that take dropest_validation_sample[]."""
+    single = len(samples) == 3 and not isinstance(samples[0], (tuple, list))
+    if single:
+        samples = (tuple(samples),)
+    opts = ValidationOpts(max_draws, round_candidates, max_keys_per_chunk)
+    arrays = [{k: np.zeros(max(1, n), t) for k, t in VALIDATION_KINDS} for _, _, n in samples]
+    S = (ValidationSample * max(1, len(samples)))()
+    for s, (lo, hi, n), a in zip(S, samples, arrays):
+        s.min_ed, s.max_ed, s.n_pairs = lo, hi, n
+        for k, _ in VALIDATION_KINDS:
+            setattr(s, k, a[k].ctypes.data)
+    return samples, single, opts, S, arrays
+
+
+def validation_results(samples, single, S, arrays):
+    """the dicts Context.merge_validation returns, from a filled ValidationSample array"""
+    outs = []
+    for _, s, a in zip(samples, S, arrays):
+        out = {k: a[k][:s.n_found] for k, _ in VALIDATION_KINDS}
+        out.update(n_found=int(s.n_found), draws_used=int(s.draws_used), complete=int(s.complete), rounds=int(s.rounds),
+                   chunks=int(s.chunks), ms_view=s.ms_view, ms_sampler=s.ms_sampler, ms_evaluation=s.ms_evaluation)
+        outs.append(out)
+    return outs[0] if single else outs
 
 
 def radix_plan(varying_mask):

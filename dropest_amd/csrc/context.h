@@ -673,11 +673,23 @@ struct dropest_ctx {
 		std::vector<uint64_t> cells;                  // filtered_cells()
 		std::vector<u32> umis;                        // their TOTAL_UMIS stat
 		u32 n_mol = 0, n_cg = 0, F = 0;
-		int umi_bits = 0;
+		int umi_bits = 0, gene_bits = 0;              // the key's UMI field (one bit wider than the pass's when override UMIs lie above it) and gene field
+		u64 gene_none = 0;
 		double ms = 0;
 	};
 	bool is_shard_ctx = false, was_split = false;     // contexts the validation refuses
 	void validation_build_view(ValidationView &V);
+	// the parts of it that a sharded run shares (shard_validation.h): the barcode rows from text, everything from the sorted view keys onwards
+	void validation_set_barcodes(ValidationView &V, const std::vector<std::string> &text);
+	void validation_finish_view(ValidationView &V);
+	// one sample's pairs on the device and the common genes of each; the chunk loop over pairs [q0, q1); the Poisson tail (validation.h)
+	struct ValidationPairs {
+		dropest::DevBuf<u32> d_pb, d_pc, d_cnt, d_inter; dropest::DevBuf<dropest::PairRange> d_pr;
+		std::vector<u32> cnt;
+	};
+	bool validation_common_genes(const ValidationView &V, const std::vector<u32> &a, const std::vector<u32> &b, ValidationPairs &P);
+	u32 validation_evaluate_range(const ValidationView &V, const dropest_validation_opts &opts, ValidationPairs &P, u32 q0, u32 q1, u32 *inter, double *expected);
+	static void validation_tail(size_t n, const u32 *inter, double *expected, double *prob);
 	void validation_sample(const ValidationView &V, const dropest_validation_opts &opts, dropest_validation_sample &S, std::vector<u32> &a, std::vector<u32> &b);
 	void validation_evaluate(const ValidationView &V, const dropest_validation_opts &opts, dropest_validation_sample &S, const std::vector<u32> &a,
 	                         const std::vector<u32> &b);

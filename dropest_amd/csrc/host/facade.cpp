@@ -1179,7 +1179,6 @@ void ResultsPrinter::save_mtx(const CellsDataContainer &c, const std::string &ba
 // reads_per_umi_per_cell) is not pinned by anything and is deterministic here: cell-id order, then gene index, then UMI.
 Rds::ValuePtr ResultsPrinter::results_list(const CellsDataContainer &c) const {
 	using namespace Rds;
-	if (validation_stats && c.sharded()) throw std::runtime_error("merge validation statistics (-S) are not built for sharded containers");
 	// DROPEST_RDS_TRACE=1: where save_results spends its time (stderr)
 	const bool rds_trace = getenv("DROPEST_RDS_TRACE") != nullptr;
 	auto rds_t0 = std::chrono::steady_clock::now();
@@ -1387,7 +1386,6 @@ Rds::ValuePtr ResultsPrinter::validation_info(const CellsDataContainer &c) const
 
 namespace Merge {
 void MergeProbabilityValidator::run_validations(const CellsDataContainer &c, const std::vector<Run> &runs) {
-	if (c.sharded()) throw std::runtime_error("merge validation statistics (-S) are not built for sharded containers");
 	if (runs.empty()) return;
 	struct Out { std::vector<uint32_t> u1, u2, ed, inter; std::vector<double> expected, prob; };
 	std::vector<Out> out(runs.size());
@@ -1403,7 +1401,10 @@ void MergeProbabilityValidator::run_validations(const CellsDataContainer &c, con
 		s.umis1 = o.u1.data(); s.umis2 = o.u2.data(); s.edit_distance = o.ed.data(); s.intersection = o.inter.data();
 		s.expected = o.expected.data(); s.probability = o.prob.data();
 	}
-	if (dropest_merge_validation_samples(c.handle(), &opts, samples.data(), uint32_t(samples.size())) != DROPEST_OK) throw std::runtime_error(dropest_last_error());
+	// a sharded container (several GPUs, or the split the facade falls back to for keys wider than 64 bits): every shard takes part, shard 0 fills the arrays
+	const dropest_status st = c.sharded() ? dropest_shard_group_merge_validation_samples(c.shard_handles().data(), int32_t(c.shard_handles().size()), &opts, samples.data(), uint32_t(samples.size()))
+	                                      : dropest_merge_validation_samples(c.handle(), &opts, samples.data(), uint32_t(samples.size()));
+	if (st != DROPEST_OK) throw std::runtime_error(dropest_last_error());
 	for (size_t k = 0; k < runs.size(); ++k) {
 		MergeProbabilityValidator &v = *runs[k].validator;
 		const size_t n = size_t(samples[k].n_found);
@@ -1420,7 +1421,7 @@ void MergeProbabilityValidator::run_validations(const CellsDataContainer &c, con
 }
 
 void MergeProbabilityValidator::run_validation(const CellsDataContainer &container, unsigned min_ed, unsigned max_ed, size_t cb_pairs_num, unsigned) {
-	if (container.filtered_cells().empty()) return;                     // MergeProbabilityValidator.cpp:11-12
+	if (!container.sharded() && container.filtered_cells().empty()) return;   // MergeProbabilityValidator.cpp:11-12 (shards: a sample of no cells finds nothing)
 	run_validations(container, {{this, min_ed, max_ed, cb_pairs_num}});
 }
 }  // namespace Merge

@@ -520,6 +520,7 @@ public:
 	s_ul_hash_t umi_distribution() const;                               // CellsDataContainer.cpp:182-197
 	const std::vector<std::string> &side_strings() const { return _side; }
 	dropest_ctx *handle() const { return _ctx; }
+	const std::vector<dropest_shard *> &shard_handles() const { return _shards; }   // empty unless sharded()
 	std::string decode(uint64_t code) const;
 };
 
@@ -529,7 +530,8 @@ namespace Merge {
 // (MergeProbabilityValidator.cpp:14) and appends to the vectors, like the reference.  The reference does not return when no pair qualifies;
 // here a run tests at most max_draws() candidate pairs (0: the library's default, 2^30) and truncated() says whether the last run stopped
 // there with fewer pairs.  run_validations: several runs over ONE view of the molecules and one set of estimator tables -- one validator per
-// run -- as save_validation_stats uses one estimator for both of its samples (ResultsPrinter.cpp:476-509).  Not on a sharded container.
+// run -- as save_validation_stats uses one estimator for both of its samples (ResultsPrinter.cpp:476-509).  A sharded container (several GPUs, or
+// the split for keys wider than 64 bits) runs them over all its shards (dropest_shard_group_merge_validation_samples): the same numbers.
 class MergeProbabilityValidator {
 public:
 	using u_vec_t = std::vector<unsigned>;
@@ -572,7 +574,7 @@ public:
 	// 1 000 000 pairs at 5 .. 100 and 100 000 at exactly 1.  max_draws caps the candidate pairs a sample tests (0: the library's default; the
 	// reference has no cap and does not return when too few pairs qualify); a sample that stopped there is written with the pairs it found and
 	// validation_truncated() says so after save_results / results_list.  The sizes are the reference's unless set otherwise (tests).  A sharded
-	// container with validation_stats throws before anything is written.
+	// container writes the same list in the same place: the statistics run over all its shards.
 	void set_validation_max_draws(uint64_t max_draws) { validation_max_draws = max_draws; }
 	void set_validation_sizes(size_t distant_pairs, size_t adjacent_pairs) { validation_distant = distant_pairs; validation_adjacent = adjacent_pairs; }
 	bool validation_truncated() const { return validation_was_truncated; }

@@ -158,4 +158,48 @@ __global__ __launch_bounds__(256) void validation_cell_rows_kernel(const unsigne
 	cell_cg_count[cell] = run_count[r];
 }
 
+// ---- the view across shards (shard_validation.h) ---------------------------------------------------------------------------------------
+// One shard's sorted view keys: first row and the row behind the last one of every cell that has rows (cell = key >> shift, a position in
+// the global filtered order; seg_begin / seg_end have one word per position and were zeroed).
+__global__ __launch_bounds__(256) void validation_cell_segments_kernel(const unsigned long long *__restrict__ keys, uint32_t n, int shift,
+                                                                       uint32_t n_cells, uint32_t *__restrict__ seg_begin,
+                                                                       uint32_t *__restrict__ seg_end) {
+	const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+	if (i >= n) return;
+	const unsigned long long cell = keys[i] >> shift;
+	if (cell >= n_cells) return;
+	if (i == 0 || (keys[i - 1] >> shift) != cell) seg_begin[cell] = i;
+	if (i + 1 == n || (keys[i + 1] >> shift) != cell) seg_end[cell] = i + 1;
+}
+
+// The all-gathered view is `world` sorted blocks, and every cell's rows lie in one of them: a cell-granular interleave, so the global order
+// is a copy of every cell's segment to its place and no sort.  Per cell: first row in the gathered buffer, rows, first row in the global
+// order.  Cells are cut into pieces of VAL_SEG rows (piece s = rows [piece_first[s], + VAL_SEG) of cell piece_cell[s]) so that one huge cell
+// is many blocks' work; a block takes pieces grid-stride.  16 bytes per lane where source and destination sit alike in their 16-byte lines
+// (both bases are 16-byte aligned, a piece starts at a multiple of VAL_SEG rows: the question is one bit per cell), 8 bytes per lane otherwise.
+constexpr uint32_t VAL_SEG = 4096;
+__global__ __launch_bounds__(256) void validation_place_kernel(const unsigned long long *__restrict__ gathered, unsigned long long *__restrict__ placed,
+                                                               const uint32_t *__restrict__ cell_src, const uint32_t *__restrict__ cell_cnt,
+                                                               const uint32_t *__restrict__ cell_dst, const uint32_t *__restrict__ piece_cell,
+                                                               const uint32_t *__restrict__ piece_first, uint32_t n_pieces) {
+	for (uint32_t s = blockIdx.x; s < n_pieces; s += gridDim.x) {
+		const uint32_t c = piece_cell[s], first = piece_first[s], cnt = cell_cnt[c];
+		if (first >= cnt) continue;
+		const uint32_t n = min(VAL_SEG, cnt - first);
+		const size_t src = size_t(cell_src[c]) + first, dst = size_t(cell_dst[c]) + first;
+		const unsigned long long *in = gathered + src;
+		unsigned long long *out = placed + dst;
+		if (((src ^ dst) & 1u) == 0) {
+			const uint32_t head = uint32_t(src & 1u);   // (n >= 1)
+			if (head && threadIdx.x == 0) out[0] = in[0];
+			const uint32_t pairs = (n - head) >> 1;
+			const ulonglong2 *in2 = reinterpret_cast<const ulonglong2 *>(in + head);
+			ulonglong2 *out2 = reinterpret_cast<ulonglong2 *>(out + head);
+			for (uint32_t i = threadIdx.x; i < pairs; i += 256) out2[i] = in2[i];
+			if (((n - head) & 1u) && threadIdx.x == 0) out[n - 1] = in[n - 1];
+		} else
+			for (uint32_t i = threadIdx.x; i < n; i += 256) out[i] = in[i];
+	}
+}
+
 }  // namespace dropest

@@ -25,6 +25,7 @@ void dropest_shard::assemble_matrix(bool filtered_m) {
 	Phase ph(this, filtered_m ? "matrix:cm" : "matrix:cm_raw");
 	const size_t ncols = order.size();
 	M.ncols = ncols; M.colptr.assign(ncols + 1, 0); M.col_barcode.resize(ncols);
+	if (filtered_m) M.col_row = order;
 	std::vector<u32> &col_cell = M.col_cell, &col_start = M.col_start;   // (members: their copies to the device are not waited for here)
 	col_cell.clear(); col_start.clear();
 	std::vector<u64> desc;

@@ -14,6 +14,7 @@
 // without a whitelist: shard_merge_free.h) -> UMI merge (N-UMIs: random fills follow ONE rand() sequence in global cell order)
 // and filter -> global column order -> every shard writes ITS columns of both matrices into host memory shared by the node's
 // shards (all PCIe links at once; shard_matrix.h).  The small kernels are in k_shard.h, the transports' test hooks in transport_test.h.
+// After a step: the merge validation statistics (-S) over all shards' filtered cells, shard_validation.h.
 #pragma once
 
 #include "transport.h"
@@ -109,6 +110,7 @@ struct dropest_shard {
 		bool shipped = false;                                     // this shard has columns on their way (the context's widening job)
 		std::vector<u32> dec_begin, dec_end;                      // this shard's columns: global begin / end of each (cm: planned on the host)
 		std::vector<u32> col_cell, col_start;                     // ... their cells and local offsets (cm; cm_raw's are in raw_plan)
+		std::vector<u32> col_row;                                 // cm: the row of G behind EVERY column (shard_validation.h)
 		dropest::PinnedBuf<u32> h_begin, h_end;                   // ... written by the device when the columns are planned there (cm_raw)
 		const unsigned long long *d_descr = nullptr; u32 nc = 0; uint64_t local_nnz = 0;   // what the fall-back needs again
 		// the byte form of a slots step, made on demand (dropest_shard_matrix_bytes)
@@ -208,6 +210,12 @@ struct dropest_shard {
 	std::vector<u64> global_ordinals(const std::vector<u32> &local_pos);
 	dropest::OrdinalMap ordinal_map() const;
 	void install_umi_hooks();
+	// merge validation statistics over all shards (shard_validation.h); COLLECTIVE
+	bool stepped = false;
+	void validation_global_view(dropest_ctx::ValidationView &V);
+	void run_merge_validation(const dropest_validation_opts *opts, dropest_validation_sample *samples, u32 n_samples);
+	bool keep_validation_keys = false;                            // option "keep_validation_keys" (test hook): the view keys of the last validation, on the host
+	std::vector<u64> val_keys_local, val_keys_placed;
 };
 
 dropest::OrdinalMap dropest_shard::ordinal_map() const {
@@ -937,6 +945,7 @@ void dropest_shard::merge_umi_distribution() {
 
 #include "shard_merge_free.h"
 #include "shard_matrix.h"
+#include "shard_validation.h"
 
 // 7. global view of the real cells: every shard's rows, all-gathered; first_global = the stream ordinal of the cell's first read
 void dropest_shard::build_global_table() {
@@ -977,6 +986,7 @@ void dropest_shard::step() {
 	using namespace dropest;
 	dropest_ctx &c = *ctx;
 	HIP_CHECK(hipSetDevice(c.cfg.device));
+	stepped = false;   // (a step that fails part way leaves nothing the validation statistics may read)
 	Phase whole(this, "step");
 	// the ordinal ranges of all shards (ordinals name reads across shards: first-seen order, N-UMI tie breaks)
 	if (pushed.n) {   // reads pushed from host memory: wait for the last batch, use the store in place
@@ -1092,6 +1102,7 @@ void dropest_shard::step() {
 		Phase ph(this, "matrix:lists"); for (int k = 0; k < 2; ++k) collect_lists(mat[k]);   // (a slots step has no byte form in the buffer: nothing to collect)
 	}
 	c.collect_timings();
+	stepped = true;
 }
 
 // N-UMI merge across shards (umi_merge_host.h): global first occurrences of the tie candidates, offsets into the ONE rand()
@@ -1552,6 +1563,7 @@ dropest_status dropest_shard_set_option(dropest_shard *s, const char *key, int64
 		else if (k == "byte_list_cap") s->byte_list_cap = value > 0 ? uint64_t((value + 15) & ~15ll) : 0;
 		else if (k == "packed_exchange") s->allow_packed = value != 0;
 		else if (k == "exact_widths") s->exact_widths = value != 0;
+		else if (k == "keep_validation_keys") s->keep_validation_keys = value != 0;
 		else if (k == "exchange_chunks") s->exchange_chunks = int(std::max<int64_t>(0, std::min<int64_t>(value, 16)));
 		else throw InvalidError("unknown shard option: " + k);
 	});

@@ -17,6 +17,81 @@
 
 #include "k_validation.h"
 
+// barcodes as text: the packed codes do not hold 'N' or other escaped barcodes
+void dropest_ctx::validation_set_barcodes(ValidationView &V, const std::vector<std::string> &text) {
+	using namespace dropest;
+	const size_t F = text.size();
+	std::vector<unsigned char> rows(F * VAL_STRIDE, 0);
+	for (size_t i = 0; i < F; ++i) {
+		const std::string &s = text[i];
+		if (s.size() >= size_t(VAL_COL)) throw UnsupportedError("merge validation takes barcodes of at most 31 characters");
+		std::memcpy(rows.data() + i * VAL_STRIDE, s.data(), s.size());
+		rows[i * VAL_STRIDE + VAL_STRIDE - 1] = (unsigned char)s.size();
+	}
+	V.barcodes.alloc(F * (VAL_STRIDE / 16));
+	upload(V.barcodes.p, rows.data(), rows.size());
+}
+
+// From the sorted view keys onwards: V.mol_key (n_mol keys, ascending; one word of room behind them), F and umi_bits are set by whoever made
+// the keys -- this context from its own tables (validation_build_view), or a shard from the blocks of all shards (shard_validation.h).
+void dropest_ctx::validation_finish_view(ValidationView &V) {
+	using namespace dropest;
+	const u32 n = V.n_mol, F = V.F;
+	V.n_cg = 0;
+	if (!n) return;
+	// (the scratch of the sorts below: a shard's own tables may be smaller than the view of all shards)
+	keys_a.ensure(n); keys_b.ensure(n); vals_a.ensure(n); vals_b.ensure(n);
+	// (cell, gene) rows: runs of key >> UMI bits, their lengths scanned into cg_mol_begin
+	DevBuf<u32> run_cnt;
+	{
+		hipLaunchKernelGGL(validation_shift_keys_kernel, dim3(div_up(n, 256)), dim3(256), 0, stream, V.mol_key.p, n, V.umi_bits, ~0ull, keys_a.p);
+		UmiRuns p{};
+		p.keys = keys_a.p;
+		V.n_cg = run_segmented_reduce(*this, "validation:cell_gene", p, n, 8, [&](u32 t) {
+			V.cg_key.alloc(size_t(t) + 1); run_cnt.alloc(size_t(t) + 1); V.cg_mol_begin.alloc(size_t(t) + 1);
+			zero_async(*this, run_cnt.p, (size_t(t) + 1) * 4);
+			p.run_key = V.cg_key.p; p.out[0] = run_cnt.p;
+		});
+		scan_counts(run_cnt.p, V.cg_mol_begin.p, V.n_cg, scalars.p);
+		HIP_CHECK(hipMemcpyAsync(V.cg_mol_begin.p + V.n_cg, &V.n_mol, 4, hipMemcpyHostToDevice, stream));
+		HIP_CHECK(stream_wait(stream));
+	}
+	// cells: runs of (cell, gene) key >> gene bits -> the row range of every rank (cells without molecules keep 0, 0)
+	{
+		V.cell_cg_begin.alloc(F); V.cell_cg_count.alloc(F);
+		zero_async(*this, V.cell_cg_begin.p, size_t(F) * 4);
+		zero_async(*this, V.cell_cg_count.p, size_t(F) * 4);
+		hipLaunchKernelGGL(validation_shift_keys_kernel, dim3(div_up(V.n_cg, 256)), dim3(256), 0, stream, V.cg_key.p, V.n_cg, V.gene_bits, ~0ull, keys_a.p);
+		UmiRuns p{};
+		p.keys = keys_a.p;
+		DevBuf<u64> run_cell; DevBuf<u32> cell_cnt, cell_begin;
+		const u32 runs = run_segmented_reduce(*this, "validation:cells", p, V.n_cg, 8, [&](u32 t) {
+			run_cell.alloc(size_t(t) + 1); cell_cnt.alloc(size_t(t) + 1); cell_begin.alloc(size_t(t) + 1);
+			zero_async(*this, cell_cnt.p, (size_t(t) + 1) * 4);
+			p.run_key = run_cell.p; p.out[0] = cell_cnt.p;
+		});
+		scan_counts(cell_cnt.p, cell_begin.p, runs, scalars.p);
+		hipLaunchKernelGGL(validation_cell_rows_kernel, dim3(div_up(runs, 256)), dim3(256), 0, stream, run_cell.p, cell_cnt.p, cell_begin.p, runs,
+		                   V.cell_cg_begin.p, V.cell_cg_count.p);
+		HIP_CHECK(hipGetLastError());
+		HIP_CHECK(stream_wait(stream));
+	}
+
+	// the estimator's tables, once: UMI fields of the view's rows -> distribution -> classes -> collisions table
+	{
+		scalars.ensure(16);
+		HIP_CHECK(hipMemsetAsync(scalars.p, 0, 16, stream));
+		hipLaunchKernelGGL(max_gene_size_kernel, dim3(div_up(V.n_cg, 256)), dim3(256), 0, stream, V.cg_key.p, V.cg_mol_begin.p, V.n_cg, V.gene_none, scalars.p + 1);
+		const u64 code_mask = V.umi_bits >= 64 ? ~0ull : ((1ull << V.umi_bits) - 1ull);
+		hipLaunchKernelGGL(validation_shift_keys_kernel, dim3(div_up(n, 256)), dim3(256), 0, stream, V.mol_key.p, n, 0, code_mask, keys_a.p);
+		HIP_CHECK(hipGetLastError());
+		u32 head[2] = {0, 0};
+		fetch(head, scalars.p, 8);
+		ptab = PoissonTables{};
+		if (head[1]) poisson_tables_from_umi_codes(n, code_mask, head[1]);
+	}
+}
+
 void dropest_ctx::validation_build_view(ValidationView &V) {
 	using namespace dropest;
 	const auto t0 = std::chrono::steady_clock::now();
@@ -24,21 +99,14 @@ void dropest_ctx::validation_build_view(ValidationView &V) {
 	V.cells = filtered_cells();
 	const u32 F = V.F = u32(V.cells.size());
 	V.n_mol = V.n_cg = 0;
+	V.gene_bits = L.gene_bits; V.gene_none = L.gene_none;
 	V.umis.resize(F);
 	for (u32 i = 0; i < F; ++i) V.umis[i] = u32(real[filtered_ridx[i]].row.total_umis);   // Cell::umis_number() = the TOTAL_UMIS stat
 	if (F < 2) return;
-
-	// barcodes as text: the packed codes do not hold 'N' or other escaped barcodes
 	{
-		std::vector<unsigned char> rows(size_t(F) * VAL_STRIDE, 0);
-		for (u32 i = 0; i < F; ++i) {
-			const std::string s = barcode_of(real[filtered_ridx[i]]);
-			if (s.size() >= size_t(VAL_COL)) throw UnsupportedError("merge validation takes barcodes of at most 31 characters");
-			std::memcpy(rows.data() + size_t(i) * VAL_STRIDE, s.data(), s.size());
-			rows[size_t(i) * VAL_STRIDE + VAL_STRIDE - 1] = (unsigned char)s.size();
-		}
-		V.barcodes.alloc(size_t(F) * (VAL_STRIDE / 16));
-		upload(V.barcodes.p, rows.data(), rows.size());
+		std::vector<std::string> text(F);
+		for (u32 i = 0; i < F; ++i) text[i] = barcode_of(real[filtered_ridx[i]]);
+		validation_set_barcodes(V, text);
 	}
 	if (!n_mol) return;
 
@@ -94,55 +162,7 @@ void dropest_ctx::validation_build_view(ValidationView &V) {
 	V.mol_key.alloc(size_t(n) + 1);
 	HIP_CHECK(hipMemcpyAsync(V.mol_key.p, k, size_t(n) * 8, hipMemcpyDeviceToDevice, stream));
 
-	// (cell, gene) rows: runs of key >> UMI bits, their lengths scanned into cg_mol_begin
-	DevBuf<u32> run_cnt;
-	{
-		hipLaunchKernelGGL(validation_shift_keys_kernel, dim3(div_up(n, 256)), dim3(256), 0, stream, V.mol_key.p, n, V.umi_bits, ~0ull, keys_a.p);
-		UmiRuns p{};
-		p.keys = keys_a.p;
-		V.n_cg = run_segmented_reduce(*this, "validation:cell_gene", p, n, 8, [&](u32 t) {
-			V.cg_key.alloc(size_t(t) + 1); run_cnt.alloc(size_t(t) + 1); V.cg_mol_begin.alloc(size_t(t) + 1);
-			zero_async(*this, run_cnt.p, (size_t(t) + 1) * 4);
-			p.run_key = V.cg_key.p; p.out[0] = run_cnt.p;
-		});
-		scan_counts(run_cnt.p, V.cg_mol_begin.p, V.n_cg, scalars.p);
-		HIP_CHECK(hipMemcpyAsync(V.cg_mol_begin.p + V.n_cg, &V.n_mol, 4, hipMemcpyHostToDevice, stream));
-		HIP_CHECK(stream_wait(stream));
-	}
-	// cells: runs of (cell, gene) key >> gene bits -> the row range of every rank (cells without molecules keep 0, 0)
-	{
-		V.cell_cg_begin.alloc(F); V.cell_cg_count.alloc(F);
-		zero_async(*this, V.cell_cg_begin.p, size_t(F) * 4);
-		zero_async(*this, V.cell_cg_count.p, size_t(F) * 4);
-		hipLaunchKernelGGL(validation_shift_keys_kernel, dim3(div_up(V.n_cg, 256)), dim3(256), 0, stream, V.cg_key.p, V.n_cg, L.gene_bits, ~0ull, keys_a.p);
-		UmiRuns p{};
-		p.keys = keys_a.p;
-		DevBuf<u64> run_cell; DevBuf<u32> cell_cnt, cell_begin;
-		const u32 runs = run_segmented_reduce(*this, "validation:cells", p, V.n_cg, 8, [&](u32 t) {
-			run_cell.alloc(size_t(t) + 1); cell_cnt.alloc(size_t(t) + 1); cell_begin.alloc(size_t(t) + 1);
-			zero_async(*this, cell_cnt.p, (size_t(t) + 1) * 4);
-			p.run_key = run_cell.p; p.out[0] = cell_cnt.p;
-		});
-		scan_counts(cell_cnt.p, cell_begin.p, runs, scalars.p);
-		hipLaunchKernelGGL(validation_cell_rows_kernel, dim3(div_up(runs, 256)), dim3(256), 0, stream, run_cell.p, cell_cnt.p, cell_begin.p, runs,
-		                   V.cell_cg_begin.p, V.cell_cg_count.p);
-		HIP_CHECK(hipGetLastError());
-		HIP_CHECK(stream_wait(stream));
-	}
-
-	// the estimator's tables, once: UMI fields of the view's rows -> distribution -> classes -> collisions table
-	{
-		scalars.ensure(16);
-		HIP_CHECK(hipMemsetAsync(scalars.p, 0, 16, stream));
-		hipLaunchKernelGGL(max_gene_size_kernel, dim3(div_up(V.n_cg, 256)), dim3(256), 0, stream, V.cg_key.p, V.cg_mol_begin.p, V.n_cg, L.gene_none, scalars.p + 1);
-		const u64 code_mask = V.umi_bits >= 64 ? ~0ull : ((1ull << V.umi_bits) - 1ull);
-		hipLaunchKernelGGL(validation_shift_keys_kernel, dim3(div_up(n, 256)), dim3(256), 0, stream, V.mol_key.p, n, 0, code_mask, keys_a.p);
-		HIP_CHECK(hipGetLastError());
-		u32 head[2] = {0, 0};
-		fetch(head, scalars.p, 8);
-		ptab = PoissonTables{};
-		if (head[1]) poisson_tables_from_umi_codes(n, code_mask, head[1]);
-	}
+	validation_finish_view(V);
 	V.ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
@@ -214,6 +234,69 @@ void dropest_ctx::validation_sample(const ValidationView &V, const dropest_valid
 	S.ms_sampler = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
+// The evaluation in three steps, so that the shards of a run can share the pairs of one sample (shard_validation.h): the common genes of
+// every pair (cheap, the same on every shard), the chunk loop over a range of the pairs, the Poisson tail of a range.
+bool dropest_ctx::validation_common_genes(const ValidationView &V, const std::vector<u32> &a, const std::vector<u32> &b, ValidationPairs &P) {
+	using namespace dropest;
+	const u32 NP = u32(a.size());
+	P.cnt.assign(NP, 0);
+	if (!NP || !V.n_mol || !ptab.ready) return false;
+	P.d_pb.alloc(NP); P.d_pc.alloc(NP); P.d_cnt.alloc(NP); P.d_inter.alloc(NP); P.d_pr.alloc(NP);
+	upload(P.d_pb.p, a.data(), size_t(NP) * 4);
+	upload(P.d_pc.p, b.data(), size_t(NP) * 4);
+	hipLaunchKernelGGL(common_genes_kernel<false>, dim3(div_up(NP, 256)), dim3(256), 0, stream, P.d_pb.p, P.d_pc.p, NP, V.cell_cg_begin.p, V.cell_cg_count.p,
+	                   V.cg_key.p, V.cg_mol_begin.p, V.gene_none, ptab.adj.p, P.d_cnt.p, nullptr, nullptr);
+	HIP_CHECK(hipGetLastError());
+	fetch(P.cnt.data(), P.d_cnt.p, size_t(NP) * 4);
+	return true;
+}
+
+// pairs [q0, q1) of P: inter / expected are the arrays of ALL pairs; returns the number of chunks
+dropest::u32 dropest_ctx::validation_evaluate_range(const ValidationView &V, const dropest_validation_opts &opts, ValidationPairs &P, u32 q0, u32 q1, u32 *inter,
+                                                    double *expected) {
+	using namespace dropest;
+	const PoissonSource src{V.cell_cg_begin.p, V.cell_cg_count.p, V.cg_key.p, V.cg_mol_begin.p, V.gene_none};
+	const std::vector<u32> &cnt = P.cnt;
+	uint64_t budget = opts.max_keys_per_chunk;
+	if (!budget) {   // a key costs about 64 bytes along the chain (keys, sort ping-pong with values, distinct keys)
+		size_t free_b = 0, total_b = 0;
+		HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+		budget = std::max<uint64_t>(uint64_t(1) << 16, free_b / 2 / 64);
+	}
+	budget = std::min<uint64_t>(budget, uint64_t(1) << 31);
+	const int low_bits = V.gene_bits + V.umi_bits;
+	const u64 low_mask = low_bits >= 64 ? ~0ull : ((1ull << low_bits) - 1ull);
+	u32 chunks = 0;
+	for (u32 p0 = q0; p0 < q1;) {
+		u32 p1 = p0;
+		uint64_t keys = 0;
+		while (p1 < q1 && (p1 == p0 || keys + cnt[p1] <= budget)) keys += cnt[p1++];
+		const u32 np = p1 - p0;
+		hipLaunchKernelGGL(pair_ranges_kernel, dim3(div_up(np, 256)), dim3(256), 0, stream, P.d_pb.p + p0, P.d_pc.p + p0, np, src.cell_cg_begin, src.cell_cg_count,
+		                   src.cg_mol_begin, P.d_pr.p);
+		HIP_CHECK(hipGetLastError());
+		timed("umig_intersect", double(np) * 64, [&] {
+			hipLaunchKernelGGL(umig_intersect_kernel, dim3(np), dim3(256), 0, stream, P.d_pr.p, np, V.mol_key.p, V.mol_key.p, low_mask, V.umi_bits,
+			                   V.gene_none, P.d_inter.p);
+		});
+		fetch(inter + p0, P.d_inter.p, size_t(np) * 4);
+		if (keys) poisson_expected_pairs(src, P.d_pb.p + p0, P.d_pc.p + p0, np, cnt.data() + p0, expected + p0);
+		++chunks;
+		p0 = p1;
+	}
+	return chunks;
+}
+
+// PoissonTargetEstimator::estimate_intersection_prob (:67-94): an empty intersection gives -1 and 1
+void dropest_ctx::validation_tail(size_t n, const u32 *inter, double *expected, double *prob) {
+	dropest::parallel_ranges(n, [&](size_t p0, size_t p1, unsigned) {
+		for (size_t p = p0; p < p1; ++p) {
+			if (inter[p] == 0) { expected[p] = -1.0; prob[p] = 1.0; }
+			else prob[p] = poisson_upper_tail(long(inter[p]), expected[p]);
+		}
+	}, 4096, dropest::HostPool::MAX);
+}
+
 void dropest_ctx::validation_evaluate(const ValidationView &V, const dropest_validation_opts &opts, dropest_validation_sample &S, const std::vector<u32> &a,
                                       const std::vector<u32> &b) {
 	using namespace dropest;
@@ -223,51 +306,9 @@ void dropest_ctx::validation_evaluate(const ValidationView &V, const dropest_val
 	if (!NP) return;
 	std::vector<u32> inter(NP, 0);
 	std::vector<double> expected(NP, 0.0), prob(NP, 1.0);
-	if (V.n_mol && ptab.ready) {
-		DevBuf<u32> d_pb, d_pc, d_cnt, d_inter; DevBuf<PairRange> d_pr;
-		d_pb.alloc(NP); d_pc.alloc(NP); d_cnt.alloc(NP); d_inter.alloc(NP); d_pr.alloc(NP);
-		upload(d_pb.p, a.data(), size_t(NP) * 4);
-		upload(d_pc.p, b.data(), size_t(NP) * 4);
-		const PoissonSource src{V.cell_cg_begin.p, V.cell_cg_count.p, V.cg_key.p, V.cg_mol_begin.p, layout.gene_none};
-		hipLaunchKernelGGL(common_genes_kernel<false>, dim3(div_up(NP, 256)), dim3(256), 0, stream, d_pb.p, d_pc.p, NP, src.cell_cg_begin, src.cell_cg_count,
-		                   src.cg_key, src.cg_mol_begin, src.gene_mask, ptab.adj.p, d_cnt.p, nullptr, nullptr);
-		HIP_CHECK(hipGetLastError());
-		std::vector<u32> cnt(NP);
-		fetch(cnt.data(), d_cnt.p, size_t(NP) * 4);
-		uint64_t budget = opts.max_keys_per_chunk;
-		if (!budget) {   // a key costs about 64 bytes along the chain (keys, sort ping-pong with values, distinct keys)
-			size_t free_b = 0, total_b = 0;
-			HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
-			budget = std::max<uint64_t>(uint64_t(1) << 16, free_b / 2 / 64);
-		}
-		budget = std::min<uint64_t>(budget, uint64_t(1) << 31);
-		const int low_bits = layout.gene_bits + V.umi_bits;
-		const u64 low_mask = low_bits >= 64 ? ~0ull : ((1ull << low_bits) - 1ull);
-		for (u32 p0 = 0; p0 < NP;) {
-			u32 p1 = p0;
-			uint64_t keys = 0;
-			while (p1 < NP && (p1 == p0 || keys + cnt[p1] <= budget)) keys += cnt[p1++];
-			const u32 np = p1 - p0;
-			hipLaunchKernelGGL(pair_ranges_kernel, dim3(div_up(np, 256)), dim3(256), 0, stream, d_pb.p + p0, d_pc.p + p0, np, src.cell_cg_begin, src.cell_cg_count,
-			                   src.cg_mol_begin, d_pr.p);
-			HIP_CHECK(hipGetLastError());
-			timed("umig_intersect", double(np) * 64, [&] {
-				hipLaunchKernelGGL(umig_intersect_kernel, dim3(np), dim3(256), 0, stream, d_pr.p, np, V.mol_key.p, V.mol_key.p, low_mask, V.umi_bits,
-				                   layout.gene_none, d_inter.p);
-			});
-			fetch(inter.data() + p0, d_inter.p, size_t(np) * 4);
-			if (keys) poisson_expected_pairs(src, d_pb.p + p0, d_pc.p + p0, np, cnt.data() + p0, expected.data() + p0);
-			++S.chunks;
-			p0 = p1;
-		}
-	}
-	// PoissonTargetEstimator::estimate_intersection_prob (:67-94): an empty intersection gives -1 and 1
-	parallel_ranges(NP, [&](size_t p0, size_t p1, unsigned) {
-		for (size_t p = p0; p < p1; ++p) {
-			if (inter[p] == 0) { expected[p] = -1.0; prob[p] = 1.0; }
-			else prob[p] = poisson_upper_tail(long(inter[p]), expected[p]);
-		}
-	}, 4096, dropest::HostPool::MAX);
+	ValidationPairs P;
+	if (validation_common_genes(V, a, b, P)) S.chunks = validation_evaluate_range(V, opts, P, 0, NP, inter.data(), expected.data());
+	validation_tail(NP, inter.data(), expected.data(), prob.data());
 	for (u32 p = 0; p < NP; ++p) {
 		if (S.intersection) S.intersection[p] = inter[p];
 		if (S.expected) S.expected[p] = expected[p];
@@ -278,8 +319,8 @@ void dropest_ctx::validation_evaluate(const ValidationView &V, const dropest_val
 
 void dropest_ctx::run_merge_validation(const dropest_validation_opts *opts_in, dropest_validation_sample *samples, u32 n_samples) {
 	using namespace dropest;
-	if (is_shard_ctx) throw UnsupportedError("merge validation statistics are not built for sharded containers: this context belongs to a shard");
-	if (was_split) throw UnsupportedError("merge validation statistics are not built for split containers: dropest_ctx_split handed this context's reads to shards");
+	if (is_shard_ctx) throw UnsupportedError("merge validation statistics are not computed by one context of a sharded run: this context belongs to a shard -- call dropest_shard_merge_validation_samples on every shard, or dropest_shard_group_merge_validation_samples");
+	if (was_split) throw UnsupportedError("merge validation statistics are not computed by a split context: dropest_ctx_split handed this context's reads to shards -- call dropest_shard_group_merge_validation_samples on them");
 	if (!initialized) throw InvalidError("You must initialize container");
 	if (n_samples && !samples) throw InvalidError("null argument");
 	const dropest_validation_opts opts = opts_in ? *opts_in : dropest_validation_opts{0, 0, 0};

@@ -89,6 +89,14 @@ class Shard:
     def set_option(self, key, value):
         self._chk(self.L.dropest_shard_set_option(self.h, key.encode(), int(value)))
 
+    def merge_validation(self, *samples, max_draws=0, round_candidates=0, max_keys_per_chunk=0):
+        """Context.merge_validation over ALL filtered cells of the run (dropest_shard_merge_validation_samples).  COLLECTIVE: every shard
+        of the run makes the same call, after a step.  Returns what Context.merge_validation returns (with rounds, chunks and the ms_*
+        fields for a single sample too); cell1 / cell2 are column indices of the filtered matrix (matrix(True)[3] names them)."""
+        samples, single, opts, S, arrays = capi.validation_request(samples, max_draws, round_candidates, max_keys_per_chunk)
+        self._chk(self.L.dropest_shard_merge_validation_samples(self.h, C.byref(opts), S, len(samples)))
+        return capi.validation_results(samples, single, S, arrays)
+
     def matrix(self, filtered):
         """(colptr u64[ncols + 1], rowidx u32[nnz], values u32[nnz], column barcodes u64[ncols]) of the GLOBAL matrix: views of
         library-owned memory, valid until the next step (meaningful on shard 0)."""
@@ -220,6 +228,15 @@ class ShardGroup:
         rc = self.L.dropest_shard_group_step(self._handles, len(self.shards))
         if rc != 0:
             raise capi.DropestError(rc, self.L.dropest_last_error().decode())
+
+    def merge_validation(self, *samples, max_draws=0, round_candidates=0, max_keys_per_chunk=0):
+        """Shard.merge_validation on every shard, one host thread each (dropest_shard_group_merge_validation_samples); the result is
+        shard 0's."""
+        samples, single, opts, S, arrays = capi.validation_request(samples, max_draws, round_candidates, max_keys_per_chunk)
+        rc = self.L.dropest_shard_group_merge_validation_samples(self._handles, len(self.shards), C.byref(opts), S, len(samples))
+        if rc != 0:
+            raise capi.DropestError(rc, self.L.dropest_last_error().decode())
+        return capi.validation_results(samples, single, S, arrays)
 
     def close(self):
         for s in self.shards:

@@ -375,7 +375,8 @@ dropest_status dropest_poisson_intersection_prob(dropest_ctx *ctx, uint64_t cell
  * Outputs, sized for n_pairs by the caller, entries [0, n_found): cell ids (not part of the reference's record), umis_number() of
  * both cells (:39-40), ed (:41), intersection size, expected size and probability (:42-44; -1 and 1 for an empty intersection).
  * Any output pointer may be null.  Needs an initialised context, before or after merge_and_filter; a shard's context and a context
- * that dropest_ctx_split emptied are refused (UNSUPPORTED).
+ * that dropest_ctx_split emptied are refused (UNSUPPORTED): their statistics come from dropest_shard_merge_validation_samples /
+ * dropest_shard_group_merge_validation_samples.
  * dropest_merge_validation_samples: several samples over one view of the molecules and one set of estimator tables, as
  * save_validation_stats runs its two over one estimator (ResultsPrinter.cpp:476-509). */
 typedef struct dropest_validation_opts {
@@ -620,6 +621,26 @@ dropest_status dropest_shard_set_umi_qualities_var(dropest_shard *shard, const u
                                                    uint64_t n_reads);
 dropest_status dropest_shard_step(dropest_shard *shard);
 dropest_status dropest_shard_group_step(dropest_shard *const *shards, int32_t n);   /* one host thread per shard */
+/* Merge validation statistics (`dropest -S`, see dropest_merge_validation_samples) over ALL filtered cells of a sharded or split run.
+ * COLLECTIVE: every shard of the run calls it with the same options and the same (min_ed, max_ed, n_pairs) of every sample, after a
+ * step (before one: DROPEST_ERR_INVALID, "You must initialize container").  The first collective compares the requests of all shards: when
+ * one differs, EVERY shard returns DROPEST_ERR_INVALID and none enters a collective its peers will not join.
+ * Every shard builds the same view of all filtered cells' molecules (8 bytes per molecule of a filtered cell on every GPU), runs the same
+ * sampler, evaluates its share of the pairs, and fills its caller's arrays IN FULL with the numbers of all pairs.
+ * cell1 / cell2 of a sharded sample are COLUMN INDICES OF THE FILTERED MATRIX (dropest_shard_matrix(shard, 1, ...): col_barcodes names
+ * them), not cell ids: the shards number their cells separately.  chunks is the sum over the shards, rounds / draws_used / n_found /
+ * complete are the sampler's (the same on every shard), the ms_* fields are the calling shard's.  The refusals of one context hold: a view
+ * key (column, gene, UMI) wider than 64 bits, 2^32 - 16 or more molecules in the view of all shards, barcodes longer than 31. */
+dropest_status dropest_shard_merge_validation_samples(dropest_shard *shard, const dropest_validation_opts *opts,
+                                                      dropest_validation_sample *samples, uint32_t n_samples);
+/* The same for the shards of one process (dropest_shard_group_create, dropest_ctx_split): one host thread per shard, errors as in
+ * dropest_shard_group_step; the caller's arrays are filled once, from shard 0. */
+dropest_status dropest_shard_group_merge_validation_samples(dropest_shard *const *shards, int32_t n, const dropest_validation_opts *opts,
+                                                            dropest_validation_sample *samples, uint32_t n_samples);
+/* How the pairs of one sample are dealt to the shards for evaluation: cnt[p] = common genes of pair p; shard r takes pairs
+ * [bounds[r], bounds[r + 1]), bounds[0] = 0, bounds[world] = n_pairs.  Range r ends behind the first pair at which the running sum of cnt
+ * reaches (r + 1) * total / world; pairs with cnt = 0 ride along; total = 0: equal numbers of pairs.  Plain host code (no device). */
+dropest_status dropest_validation_cut_pairs(const uint32_t *cnt, uint64_t n_pairs, int32_t world, uint64_t *bounds /* world + 1 */);
 /* The step ENDS with rowidx / values filled (shard options "byte_matrix" and "slots_matrix", both on by default): the 32-bit dgCMatrix
  * slots i / x of ResultsPrinter::create_matrix (Estimation/ResultsPrinter.cpp:433-442) in the node-shared host buffer -- every shard's
  * columns cross ITS PCIe link as bytes and are widened into the shared slots by that shard's host threads while the next chunk of
