@@ -129,6 +129,7 @@ def lib():
         "dropest_chr_stats": (C.c_int, [vp, u64p, vp, vp, vp, vp]),
         "dropest_count_matrix_csc_levels": (C.c_int, [vp, C.c_char_p, C.c_int, u64p, u64p, P(vp), P(vp), P(vp)]),
         "dropest_merge_target": (C.c_int, [vp, C.c_uint64, P(C.c_int64)]),
+        "dropest_simple_merge_pairs": (C.c_int, [vp, u64p, vp, vp, vp, vp]),
         "dropest_exclude_cell": (C.c_int, [vp, C.c_uint64]), "dropest_merge_cells": (C.c_int, [vp, C.c_uint64, C.c_uint64]),
         "dropest_merge_umis": (C.c_int, [vp, C.c_uint64, C.c_uint32, C.c_uint64, vp, vp]),
         "dropest_add_umi_to_cell": (C.c_int, [vp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, vp, C.c_uint32]),
@@ -254,7 +255,7 @@ EXPORTED_SYMBOLS = [
     "dropest_set_umi_qualities", "dropest_umi_quality_length", "dropest_cell_molecule_qualities",
     "dropest_set_umi_qualities_var", "dropest_cell_molecule_quality_lengths",
     "dropest_exclude_cell", "dropest_merge_cells", "dropest_merge_umis",
-    "dropest_chr_stats", "dropest_merge_target", "dropest_kernel_stats", "dropest_set_profiling", "dropest_set_profiling_filter", "dropest_prefetch_raw_matrix", "dropest_radix_plan", "dropest_stream",
+    "dropest_chr_stats", "dropest_merge_target", "dropest_simple_merge_pairs", "dropest_kernel_stats", "dropest_set_profiling", "dropest_set_profiling_filter", "dropest_prefetch_raw_matrix", "dropest_radix_plan", "dropest_stream",
     "dropest_sort_layout", "dropest_host_register", "dropest_host_unregister", "dropest_ingest", "dropest_ingest_summary_get", "dropest_ingest_summary_set",
     "dropest_gene_chr_table", "dropest_shard_merge_search", "dropest_shard_merge_pairs", "dropest_shard_merge_export",
     "dropest_shard_merge_intersect", "dropest_shard_merge_decide", "dropest_merge_apply", "dropest_shard_merge_finish",
@@ -673,6 +674,18 @@ class Context:
         t = C.c_int64()
         self._chk(self.L.dropest_merge_target(self.h, cell, C.byref(t)))
         return t.value
+
+    def simple_merge_pairs(self):
+        """(base, other, shared, distance) of the Simple / PoissonSimple pair table on the un-merged state; distance 0xFFFFFFFF = the
+        host computes it (an escaped barcode, more than 31 bases)."""
+        n = C.c_uint64()
+        self._chk(self.L.dropest_simple_merge_pairs(self.h, C.byref(n), None, None, None, None))
+        base = np.zeros(n.value, np.uint64); other = np.zeros(n.value, np.uint64)
+        shared = np.zeros(n.value, np.uint32); distance = np.zeros(n.value, np.uint32)
+        if n.value:
+            self._chk(self.L.dropest_simple_merge_pairs(self.h, C.byref(n), base.ctypes.data, other.ctypes.data, shared.ctypes.data,
+                                                        distance.ctypes.data))
+        return base, other, shared, distance
 
     def exclude_cell(self, cell):
         self._chk(self.L.dropest_exclude_cell(self.h, cell))

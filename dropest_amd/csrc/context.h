@@ -724,12 +724,18 @@ struct dropest_ctx {
 	} ms;
 	void run_cb_merge_real();
 	void run_cb_merge_simple();                  // SimpleMergeStrategy (simple_merge.h)
+	void simple_merge_targets(std::vector<u32> &cells, std::vector<u32> &tgt_id, SimplePairs &P);   // its steps 1-4: no cell changes
+	// get_merge_target of the whitelist-free strategies for every filtered cell, as dropest_merge_target / dropest_simple_merge_pairs
+	// show them: computed by the merge's own steps on first use, kept until the container changes (request_filtered)
+	struct StrategyTargets { bool valid = false; std::vector<u32> cells, target; SimplePairs P; } strategy_targets;
+	const StrategyTargets &need_strategy_targets();
 	struct SimpleReplayInput { std::vector<u64> query; std::vector<std::vector<u32>> in_order; };
 	void simple_pair_table(const u64 *sorted, u32 n_valid, int cell_bits, const u32 *d_cell_size, const u64 *d_cell_code, SimplePairs &P,
 	                       dropest::DevBuf<u64> *d_run_key, dropest::DevBuf<u32> *d_run_cnt, u32 *n_runs = nullptr);
 	void simple_pairs_to_host(const u64 *d_run_key, const u32 *d_run_cnt, u32 runs, const u64 *d_cell_code, SimplePairs &P);
 	void simple_replay_local(const std::vector<u32> &bases, SimpleReplayInput &R, bool globalize);
 	void run_cb_merge_all();                     // MergeAllMergeStrategy (merge_all.h)
+	void merge_all_filtered_targets(std::vector<u32> &target_pos);
 	void merge_all_targets(std::vector<u64> code, const std::vector<int32_t> &umis, const std::function<std::string(u32)> &text,
 	                       const std::vector<u32> *bases, std::vector<u32> &target_pos);
 	// public mutators of the container (mutate_host.h)

@@ -282,7 +282,7 @@ void dropest_ctx::free_results() {
 	shard.reset();
 	n_cells = n_mol = n_cg = n_chr_rows = 0;
 	cb_mirror.clear(); real_pristine = false;
-	real.clear(); filtered.clear(); filtered_valid = false; merge_pairs.clear(); reassign.clear(); umi_overrides.clear(); n_real_now = 0;
+	real.clear(); filtered.clear(); filtered_valid = false; strategy_targets = StrategyTargets(); merge_pairs.clear(); reassign.clear(); umi_overrides.clear(); n_real_now = 0;
 	merge_rank.clear(); reagg_prio = nullptr; extra_excluded.clear(); explicit_sources.clear(); mol_sorted_rows = 0xFFFFFFFFu;
 	layout = dropest::KeyLayout{}; umi_clean_bits = 0; umi_sentinel_stripped = false; chr_from_gene = false;   // nothing of the previous pass's key plan survives
 	umi_dict_on = false; umi_dict_n = 0; umi_dict_host.clear();
@@ -1531,6 +1531,7 @@ void dropest_ctx::fetch_real_cells(bool at_init) {
 void dropest_ctx::request_filtered(u32 genes_threshold, int max_cells) {
 	// the real-cell count is cheap and always current; the ordering is produced when somebody reads it
 	filtered_threshold = genes_threshold; filtered_max_cells = max_cells; filtered_valid = false;
+	strategy_targets = StrategyTargets();
 	n_real_now = 0;
 	constexpr unsigned W = dropest::HostPool::MAX;
 	uint64_t part[W + 1] = {0};   // (2.4e6 rows at C3 size: a millisecond or two for one thread)
@@ -2716,16 +2717,61 @@ dropest_status dropest_merge_validation(dropest_ctx *ctx, uint32_t min_ed, uint3
 	});
 }
 
+const dropest_ctx::StrategyTargets &dropest_ctx::need_strategy_targets() {
+	StrategyTargets &T = strategy_targets;
+	if (T.valid) return T;
+	if (cfg.merge_kind == DROPEST_MERGE_ALL) {
+		const std::vector<uint64_t> &order = filtered_cells();
+		T.cells.assign(order.begin(), order.end());
+		T.P = SimplePairs();
+		std::vector<u32> pos;
+		merge_all_filtered_targets(pos);
+		T.target = T.cells;
+		for (size_t f = 0; f < pos.size(); ++f) if (pos[f] != 0xFFFFFFFFu) T.target[f] = T.cells[pos[f]];
+	} else {
+		simple_merge_targets(T.cells, T.target, T.P);
+	}
+	T.valid = true;
+	collect_timings();
+	return T;
+}
+
 dropest_status dropest_merge_target(dropest_ctx *ctx, uint64_t cell, int64_t *target) {
 	return guarded([&] {
 		need_init(ctx);
 		if (ctx->merged) throw InvalidError("merge targets are defined on the un-merged state (call before merge_and_filter)");
-		if (ctx->cfg.merge_kind != DROPEST_MERGE_REAL_BARCODES && ctx->cfg.merge_kind != DROPEST_MERGE_POISSON_REAL) {
+		const int kind = ctx->cfg.merge_kind;
+		if (kind == DROPEST_MERGE_NONE) {
 			*target = int64_t(cell);   // DummyMergeStrategy
 			return;
 		}
 		if (cell >= ctx->n_cells) throw RangeError("cell index out of range");
+		if (kind == DROPEST_MERGE_SIMPLE || kind == DROPEST_MERGE_POISSON_SIMPLE || kind == DROPEST_MERGE_ALL) {
+			if (ctx->hooks) throw InvalidError("merge targets of a shard are decided by the sharded run");
+			const dropest_ctx::StrategyTargets &T = ctx->need_strategy_targets();
+			for (size_t f = 0; f < T.cells.size(); ++f)
+				if (T.cells[f] == u32(cell)) { *target = int64_t(T.target[f]); return; }
+			throw InvalidError("merge targets of this strategy are defined for filtered cells");
+		}
 		*target = ctx->compute_merge_targets(std::vector<u32>{u32(cell)}, std::vector<u32>{ctx->real_at(u32(cell))})[0];
+	});
+}
+
+dropest_status dropest_simple_merge_pairs(dropest_ctx *ctx, uint64_t *n, uint64_t *base, uint64_t *other, uint32_t *shared, uint32_t *distance) {
+	return guarded([&] {
+		need_init(ctx);
+		if (!n) throw InvalidError("null argument");
+		if (ctx->merged) throw InvalidError("the pair table is defined on the un-merged state (call before merge_and_filter)");
+		if (ctx->cfg.merge_kind != DROPEST_MERGE_SIMPLE && ctx->cfg.merge_kind != DROPEST_MERGE_POISSON_SIMPLE)
+			throw InvalidError("the pair table belongs to the Simple and PoissonSimple merges");
+		if (ctx->hooks) throw InvalidError("the pair table of a shard is partial");
+		const SimplePairs &P = ctx->need_strategy_targets().P;
+		if (base && other && shared && distance)
+			for (size_t p = 0; p < P.key.size(); ++p) {
+				base[p] = P.key[p] >> 32; other[p] = P.key[p] & 0xFFFFFFFFull;
+				shared[p] = P.cnt[p]; distance[p] = P.ed[p];
+			}
+		*n = P.key.size();
 	});
 }
 

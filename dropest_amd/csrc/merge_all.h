@@ -115,20 +115,27 @@ void dropest_ctx::merge_all_targets(std::vector<u64> code, const std::vector<int
 	}
 }
 
-void dropest_ctx::run_cb_merge_all() {
-	using namespace dropest;
-	HostStage hs(this, "cb_merge");
-	const std::vector<uint64_t> &order = filtered_cells();
-	std::vector<u32> cells(order.begin(), order.end());
-	const std::vector<u32> ridx = filtered_ridx;
-	const u32 F = u32(cells.size()), nR = u32(real.size());
-	clear_strategy_pairs();
-	if (F == 0) return;
+// get_merge_target of every filtered cell on the un-merged state, as positions in the filtered order (0xFFFFFFFF = the cell itself)
+void dropest_ctx::merge_all_filtered_targets(std::vector<u32> &target_pos) {
+	filtered_cells();
+	const std::vector<u32> &ridx = filtered_ridx;
+	const u32 F = u32(ridx.size());
 	std::vector<u64> code(F);
 	std::vector<int32_t> umis(F);
 	for (u32 f = 0; f < F; ++f) { code[f] = u64(real[ridx[f]].row.barcode); umis[f] = real[ridx[f]].row.total_umis; }
-	std::vector<u32> target_pos;
 	merge_all_targets(code, umis, [&](u32 f) { return barcode_of(real[ridx[f]]); }, nullptr, target_pos);
+}
+
+void dropest_ctx::run_cb_merge_all() {
+	using namespace dropest;
+	HostStage hs(this, "cb_merge");
+	filtered_cells();
+	const std::vector<u32> ridx = filtered_ridx;
+	const u32 F = u32(ridx.size()), nR = u32(real.size());
+	clear_strategy_pairs();
+	if (F == 0) return;
+	std::vector<u32> target_pos;
+	merge_all_filtered_targets(target_pos);
 
 	// MergeStrategyBase::merge_inited second loop
 	HostStage hs3(this, "cb_merge:apply");

@@ -14,7 +14,7 @@
 // of the others; otherwise the reference's answer depends on the iteration order of two std::unordered containers
 // keyed by cell id, and those bases are replayed with the same containers filled in the same order (the members of
 // each UMI-gene come from the sorted table, the base's UMIs in (gene index, UMI first occurrence) order).
-// No reference test pins this strategy; DESIGN.md §2b says how it is checked.
+// No reference test pins this strategy; DESIGN.md §4 says how it is checked.
 #pragma once
 
 namespace {
@@ -387,13 +387,15 @@ void dropest_ctx::simple_replay_local(const std::vector<u32> &bases, SimpleRepla
 }
 
 
-void dropest_ctx::run_cb_merge_simple() {
-	HostStage hs(this, "cb_merge");
+// Steps 1-4 of the strategy: get_merge_target of every filtered cell on the un-merged state.  cells = the filtered order,
+// tgt_id[f] = the target of cells[f] as a cell id (the cell itself: none), P = the pair table the decisions were taken from.
+// run_cb_merge_simple applies them; dropest_merge_target and dropest_simple_merge_pairs show them.
+void dropest_ctx::simple_merge_targets(std::vector<u32> &cells, std::vector<u32> &tgt_id, SimplePairs &P) {
 	const std::vector<uint64_t> &order = filtered_cells();
-	std::vector<u32> cells(order.begin(), order.end());
-	const std::vector<u32> ridx = filtered_ridx;
-	const u32 F = u32(cells.size()), nR = u32(real.size());
-	clear_strategy_pairs();
+	cells.assign(order.begin(), order.end());
+	tgt_id = cells;
+	P = SimplePairs();
+	const u32 F = u32(cells.size());
 	if (F == 0 || n_mol == 0) return;
 	const int low_bits = layout.umi_bits + layout.gene_bits;
 
@@ -423,7 +425,6 @@ void dropest_ctx::run_cb_merge_simple() {
 	}
 
 	// 2. shared UMI-genes: ordered pairs per run, sorted, run-length encoded
-	SimplePairs P;
 	simple_pair_table(sorted, n_valid, layout.cell_bits, cell_n_genes.p, cell_cb.p, P, nullptr, nullptr);
 
 	// 3. decisions for the bases whose answer does not depend on the iteration order of common_umigs_per_cell
@@ -436,7 +437,7 @@ void dropest_ctx::run_cb_merge_simple() {
 	C.container_id = [](u32 cell) { return size_t(cell); };
 	C.from_container_id = [](size_t id) { return u32(id); };
 	const bool poisson = cfg.merge_kind == DROPEST_MERGE_POISSON_SIMPLE;
-	std::vector<u32> tgt_id(cells), nb_count(F, 0), replay;
+	std::vector<u32> nb_count(F, 0), replay;
 	simple_decide(cfg, poisson, P, C, [&](const std::vector<u32> &pb, const std::vector<u32> &pc) {
 		std::vector<double> ex = poisson_expected_intersections(pb, pc);
 		if (sorted_keep.p) sorted = sorted_keep.p;
@@ -471,6 +472,17 @@ void dropest_ctx::run_cb_merge_simple() {
 		for (size_t r = 0; r < replay.size(); ++r)
 			tgt_id[rank_of[replay[r]]] = simple_replay_base(cfg, poisson, replay[r], R.in_order[r], members, q_off, q_cnt, C, P, nb_count[rank_of[replay[r]]]);
 	}
+}
+
+void dropest_ctx::run_cb_merge_simple() {
+	HostStage hs(this, "cb_merge");
+	std::vector<u32> cells, tgt_id;
+	SimplePairs P;
+	clear_strategy_pairs();
+	simple_merge_targets(cells, tgt_id, P);
+	const std::vector<u32> ridx = filtered_ridx;
+	const u32 F = u32(cells.size()), nR = u32(real.size());
+	if (F == 0 || n_mol == 0) return;
 	std::vector<int64_t> target(F);
 	for (u32 f = 0; f < F; ++f) target[f] = int64_t(real_at(tgt_id[f]));
 

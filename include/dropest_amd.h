@@ -403,9 +403,20 @@ dropest_status dropest_merge_validation(dropest_ctx *ctx, uint32_t min_ed, uint3
 dropest_status dropest_merge_validation_samples(dropest_ctx *ctx, const dropest_validation_opts *opts,
                                                 dropest_validation_sample *samples, uint32_t n_samples);
 
-/* RealBarcodesMergeStrategy::get_merge_target (RealBarcodesMergeStrategy.cpp:22-29) for one cell,
- * evaluated on the un-merged state; valid between set_initialized and merge_and_filter. */
+/* The strategy's get_merge_target for one cell, evaluated on the un-merged state; valid between set_initialized and
+ * merge_and_filter.  DROPEST_MERGE_REAL_BARCODES / _POISSON_REAL: RealBarcodesMergeStrategy.cpp:22-29, any cell.
+ * DROPEST_MERGE_SIMPLE / _POISSON_SIMPLE / _ALL: SimpleMergeStrategy.cpp:47-86, PoissonSimpleMergeStrategy.cpp:15-43,
+ * MergeAllMergeStrategy.h:16-50 for a filtered cell (any other cell: DROPEST_ERR_INVALID) -- the targets of all filtered cells
+ * are computed by the steps of the merge itself on the first call and kept until the container changes.
+ * DROPEST_MERGE_NONE: the cell itself (DummyMergeStrategy). */
 dropest_status dropest_merge_target(dropest_ctx *ctx, uint64_t cell, int64_t *target);
+/* The table the Simple and PoissonSimple merges decide from, on the un-merged state: one record per ordered pair of filtered cells
+ * (base, other != base, genes(other) >= genes(base)) that share a UMI-gene, ascending (base, other); shared = the number of UMI-genes
+ * in common (SimpleMergeStrategy::get_cells_with_common_umigs), distance = Tools::edit_distance of the two barcodes as the device
+ * computed it, 0xFFFFFFFF where it is left to the host (an escaped barcode, a barcode of more than 31 bases).  Two calls as with
+ * dropest_count_matrix: null arrays give *n. */
+dropest_status dropest_simple_merge_pairs(dropest_ctx *ctx, uint64_t *n, uint64_t *base, uint64_t *other, uint32_t *shared,
+                                          uint32_t *distance);
 
 /* ---- multi-GPU building blocks (the reference has no distributed runtime) ----------------------
  * Reads are sharded by barcode: owner(cb) = dropest_owner_of(cb, n_parts).  All pointers are DEVICE pointers on

@@ -88,6 +88,8 @@ def oracle_lib():
         "orc_poisson_expected_intersection": (C.c_double, [vp, u64, u64]),
         "orc_poisson_merge_target": (C.c_long, [vp, u64]),
         "orc_poisson_upper_tail": (C.c_double, [C.c_long, C.c_double]),
+        "orc_strategy_merge_target": (C.c_long, [vp, u64]),
+        "orc_common_umigs": (C.c_int64, [vp, u64, vp, vp, u64]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -297,6 +299,23 @@ class Oracle:
         if r == -2:
             raise RuntimeError(self.L.orc_last_error().decode())
         return r
+
+    def strategy_merge_target(self, cell):
+        """get_merge_target of the Simple, PoissonSimple or merge-all strategy (by merge_kind) for one cell, before the merge"""
+        r = int(self.L.orc_strategy_merge_target(self.h, cell))
+        if r == -2:
+            raise RuntimeError(self.L.orc_last_error().decode())
+        return r
+
+    def common_umigs(self, base):
+        """SimpleMergeStrategy::get_cells_with_common_umigs as {other: count}"""
+        n = int(self.L.orc_common_umigs(self.h, base, None, None, 0))
+        if n < 0:
+            raise RuntimeError(self.L.orc_last_error().decode())
+        others = np.zeros(n, np.uint64); counts = np.zeros(n, np.uint64)
+        if n:
+            self.L.orc_common_umigs(self.h, base, others.ctypes.data, counts.ctypes.data, n)
+        return {int(o): int(k) for o, k in zip(others, counts)}
 
     def real_neighbours(self, cell):
         out = np.zeros(4096, np.uint64)

@@ -1119,6 +1119,28 @@ double orc_poisson_expected_intersection(void *h, uint64_t c1, uint64_t c2) {   
 long orc_poisson_merge_target(void *h, uint64_t cell) {
 	try { return static_cast<orc::Container *>(h)->poisson_merge_target(cell); } catch (const std::exception &e) { g_err = e.what(); return -2; }
 }
+// the per-base entry of the whitelist-free strategies on the un-merged state (merge_kind 2, 4, 5), and the map that the two
+// Simple kinds decide from; the inverted index is built when it is not there (run_cb_merge clears it)
+long orc_strategy_merge_target(void *h, uint64_t cell) {
+	try {
+		auto *c = static_cast<orc::Container *>(h);
+		const int kind = c->cfg.merge_kind;
+		if (kind != 2 && kind != 4 && kind != 5) throw std::runtime_error("not a whitelist-free merge strategy");
+		if (kind != 5 && c->cell_ids_by_umig.empty()) c->simple_init();
+		if (kind == 4 && c->umi_probs.empty()) c->poisson_init();
+		return kind == 5 ? c->merge_all_target(cell) : kind == 4 ? c->poisson_simple_merge_target(cell) : c->simple_merge_target(cell);
+	} catch (const std::exception &e) { g_err = e.what(); return -2; }
+}
+int64_t orc_common_umigs(void *h, uint64_t base, uint64_t *others, uint64_t *counts, uint64_t cap) {
+	try {
+		auto *c = static_cast<orc::Container *>(h);
+		if (c->cell_ids_by_umig.empty()) c->simple_init();
+		const auto common = c->cells_with_common_umigs(base);
+		size_t i = 0;
+		for (auto const &it : common) { if (i < cap) { others[i] = it.first; counts[i] = it.second; } ++i; }
+		return int64_t(common.size());
+	} catch (const std::exception &e) { g_err = e.what(); return -1; }
+}
 double orc_poisson_upper_tail(long k, double lambda) { return orc::Container::poisson_upper_tail(k, lambda); }
 
 unsigned orc_edit_distance(const char *a, const char *b, int skip_n, unsigned max_ed) { return orc::edit_distance(a, b, skip_n != 0, max_ed); }

@@ -65,6 +65,18 @@ static void testRealNeighbours() {   // :227-235
 	for (size_t i = 0; i < 6; ++i) CHECK_EQ(f.container_full->get_merge_target(i), expect[i]);
 }
 
+// get_merge_target of a strategy without a whitelist (SimpleMergeStrategy.cpp:47-86): the smaller cell shares its one UMI-gene with the
+// larger one a substitution away -- 0.5 * 1 * (1/1 + 1/2) = 0.75 -- and the larger one has no candidate
+static void testSimpleMergeTarget() {
+	CellsDataContainer c(std::make_shared<Merge::SimpleMergeStrategy>(0, 0, 2, 0.2), std::make_shared<Merge::UMIs::MergeUMIsStrategySimple>(1),
+	                     Mark::get_by_code(Mark::DEFAULT_CODE));
+	c.add_record(read_info("AAATTAGGTCCA", "AAACCT", "Gene1")); c.add_record(read_info("AAATTAGGTCCA", "CCCCCT", "Gene2"));
+	c.add_record(read_info("AAATTAGGTCCC", "AAACCT", "Gene1"));
+	c.set_initialized();
+	CHECK_EQ(c.get_merge_target(1), long(0));
+	CHECK_EQ(c.get_merge_target(0), long(0));
+}
+
 static void testMergeByRealBarcodes() {   // :237-280
 	Fixture f;
 	auto &c = *f.container_full;
@@ -538,6 +550,7 @@ int main(int argc, char **argv) {
 	const std::string tmp = argc > 2 ? argv[2] : "/tmp";
 	try {
 		testRealNeighbours();
+		testSimpleMergeTarget();
 		testMergeByRealBarcodes();
 		testUmiExclusion();
 		testUMIMergeStrategySimple();

@@ -16,6 +16,7 @@ from functools import lru_cache, partial
 import numpy as np
 
 import poisson_model as pm
+import simple_merge_model as smm
 import whitelist_model as wm
 
 ACGT = "ACGT"
@@ -166,10 +167,7 @@ class ContainerCase:
             pieces = wm.split_barcode(wm.CONST, self.parts, self.barcodes[base])
             level = lambda c: sum(wm.edit_distance(x, y) for x, y in zip(pieces, wm.split_barcode(wm.CONST, self.parts, self.barcodes[c])))
             return s.candidates, [level(c) for c in s.candidates]
-        mine = self.container[base]
-        found = [c for c in self.filtered if c != base and self.n_genes[c] >= self.n_genes[base]
-                 and any(g in self.container[c] and mine[g] & self.container[c][g] for g in mine)
-                 and wm.edit_distance(self.barcodes[base], self.barcodes[c]) <= self.max_ed]
+        found = smm.poisson_simple_neighbours(self, base, self.max_ed)
         return (found, [0] * len(found)) if found else None               # an unordered_map's order: not known
 
     @lru_cache(maxsize=None)
