@@ -59,6 +59,56 @@ def test_every_fan_out(splitter, monkeypatch, tb):
         tp._both(dict(n_cells=60, n_genes=4000, umi_len=12), 150_000, 20, 50)
 
 
+def _both_profiled(stream_kw, n_reads, min_before, min_after, edit=None):
+    """tp._both with the kernel statistics on; edit(cb, umi, gene, aux) may change the stream in place before it is made canonical."""
+    arrays = SynthStream(n_reads=n_reads, **stream_kw).generate_host()
+    if edit:
+        edit(*arrays)
+    cb, umi, gene, aux = parity.canonical_stream(*arrays)
+    o = parity.oracle_run(Oracle, dict(merge_kind=0, min_genes_before=min_before, min_genes_after=min_after), cb, umi, gene, aux)
+    c = parity.gpu_run(dict(merge_kind=capi.MERGE_NONE, min_genes_before_merge=min_before, min_genes_after_merge=min_after),
+                       cb, umi, gene, aux, profile=True)
+    parity.compare(o, c)
+    return o, c
+
+
+def test_counting_partitions_with_the_1024_bucket_kernels(monkeypatch):
+    """2^10 x 2^10 buckets and no reservation: the histogram, scan and scatter kernels of both levels in their MAXF = 1024 form, on keys only
+    and on key + mark byte records."""
+    monkeypatch.setenv("DROPEST_SORT", "splitter")
+    monkeypatch.setenv("DROPEST_SS_NO_RESERVE", "1")
+    monkeypatch.setenv("DROPEST_SSORT_TB", "20")
+    o, c = _both_profiled(dict(n_cells=60, n_genes=3000), 300_000, 10, 30)
+    assert "ss_hist:L1" in c.kernel_stats() and c.sort_layout()["sort"] == "splitter" and c.sort_layout()["value_bytes"] == 0
+    monkeypatch.setenv("DROPEST_FORCE_BYTE_VALUES", "1")
+    o, c = _both_profiled(dict(n_cells=60, n_genes=4000, umi_len=12), 150_000, 20, 50)
+    assert "ss_hist:L1" in c.kernel_stats() and c.sort_layout()["sort"] == "splitter" and c.sort_layout()["value_bytes"] == 1
+
+
+def test_cell_gene_table_by_seg_reduce_behind_the_splitter_sort(splitter, monkeypatch):
+    """DROPEST_SS_NO_FUSED_CG=1: the compaction writes the molecule table alone, seg_count + seg_reduce make the (cell, gene) table from it."""
+    monkeypatch.setenv("DROPEST_SS_NO_FUSED_CG", "1")
+    o, c = _both_profiled(dict(n_cells=40, n_genes=3000), 100_000, 20, 100)
+    names = set(c.kernel_stats())
+    assert c.sort_layout()["sort"] == "splitter" and "ss_compact" in names and "ss_compact:cell_gene" not in names, names
+
+
+def test_medium_and_big_buckets_with_the_mark_byte(splitter, monkeypatch):
+    """Buckets beyond the small finishing launch, listed by the host, in the key + mark byte layout.  (The fourth stream of
+    test_buckets_beyond_the_lds_sort_fall_back draws a chromosome per read, so its genes sit on several chromosomes and it takes the
+    general layout and the LSD sort: a v3 stream with one molecule of 6 000 reads -- a big bucket -- and one of 3 000 -- a medium one --
+    stands in for it.)"""
+    monkeypatch.setenv("DROPEST_FORCE_BYTE_VALUES", "1")
+
+    def two_hot_molecules(cb, umi, gene, aux):
+        with_gene = np.flatnonzero(gene != capi.NO_GENE)
+        for src, lo, hi in ((with_gene[0], 10_000, 16_000), (with_gene[1], 20_000, 23_000)):
+            for a in (cb, umi, gene, aux):
+                a[lo:hi] = a[src]
+    o, c = _both_profiled(dict(n_cells=40, n_genes=3000, umi_len=12), 100_000, 10, 30, edit=two_hot_molecules)
+    assert c.sort_layout()["sort"] == "splitter" and c.sort_layout()["value_bytes"] == 1 and "ss_local:big" in c.kernel_stats()
+
+
 def test_key_plus_mark_byte_layout(splitter, monkeypatch):
     """C3's layout (the key uses all 64 bits, the mark travels as one byte) forced on a small v3 stream."""
     monkeypatch.setenv("DROPEST_FORCE_BYTE_VALUES", "1")
