@@ -84,6 +84,8 @@ def build_facade(force=False, verbose=False):
     src = os.path.join(CSRC, "host", "facade.cpp")
     rds = os.path.join(CSRC, "host", "rds_writer.cpp")
     bam = os.path.join(CSRC, "host", "bam_ingest.cpp")
+    bam_ctl = os.path.join(CSRC, "host", "bam_controller.cpp")
+    bam_dev = os.path.join(CSRC, "host", "bam_device.cpp")
     ga = os.path.join(CSRC, "host", "gene_annotation.cpp")
     hdr = os.path.join(CSRC, "host", "facade.h")
     test_src = os.path.join(HERE, "..", "tests", "cpp", "test_facade.cpp")
@@ -93,7 +95,8 @@ def build_facade(force=False, verbose=False):
     sharded_bam_src = os.path.join(HERE, "..", "tests", "cpp", "bam_sharded_device.cpp")
     validation_src = os.path.join(HERE, "..", "tests", "cpp", "validation_to_rds.cpp")
     validation_sharded_src = os.path.join(HERE, "..", "tests", "cpp", "validation_sharded_to_rds.cpp")
-    newest = max(os.path.getmtime(x) for x in (src, rds, bam, ga, os.path.join(CSRC, "host", "rds_writer.h"), os.path.join(CSRC, "host", "bam_ingest.h"),
+    newest = max(os.path.getmtime(x) for x in (src, rds, bam, bam_ctl, bam_dev, ga, os.path.join(CSRC, "host", "rds_writer.h"), os.path.join(CSRC, "host", "bam_ingest.h"),
+                                               os.path.join(CSRC, "host", "bam_parse.h"), os.path.join(CSRC, "host", "bgzf_blocks.h"),
                                                os.path.join(CSRC, "host", "gene_annotation.h"),
                                                hdr, test_src, bam_tool_src, rate_src, rds_tool_src, sharded_bam_src, validation_src, validation_sharded_src, LIB))
     if not force and os.path.exists(FACADE_LIB) and os.path.exists(FACADE_TEST) and os.path.exists(BAM_TOOL) and os.path.exists(RATE_TOOL) and os.path.exists(RDS_TOOL) and \
@@ -102,7 +105,7 @@ def build_facade(force=False, verbose=False):
                 os.path.getmtime(SHARDED_BAM_TOOL), os.path.getmtime(VALIDATION_TOOL), os.path.getmtime(VALIDATION_SHARDED_TOOL)) > newest:
         return FACADE_LIB, FACADE_TEST
     cmds = [
-        ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", src, rds, bam, ga, "-o", FACADE_LIB, "-L" + LIB_DIR, "-ldropest_amd", "-lz",
+        ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", src, rds, bam, bam_ctl, bam_dev, ga, "-o", FACADE_LIB, "-L" + LIB_DIR, "-ldropest_amd", "-lz",
          "-lpthread", "-Wl,-rpath,$ORIGIN"],
         ["g++", "-O2", "-std=c++17", "-Wall", test_src, "-o", FACADE_TEST, "-L" + LIB_DIR, "-ldropest_facade", "-ldropest_amd",
          "-Wl,-rpath,$ORIGIN/../../dropest_amd/lib"],

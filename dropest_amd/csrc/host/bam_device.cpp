@@ -1,0 +1,631 @@
+// bam_device.cpp -- the device path of BamController::parse_bam_files (bam_ingest.h; include/dropest_bgzf.h; DROPEST_BAM_DEVICE=1 or
+// BamController::set_device_decode).
+// The blocks are inflated on the GPU (csrc/k_inflate.h: a wave per block), the chain of records is found and every record's tags
+// are walked there (csrc/k_bamparse.h: a lane per record); 39 bytes per record come back instead of the ~300 of the record.  The
+// dictionaries stay here: the workers turn gene hashes and reference ids into indices, and the records that bring something NEW
+// (a gene name, a chromosome, a string with N) are fetched as bytes and go through RecordParser + intern_new in file order,
+// exactly like the Needs of BulkWindow.  Windows grow from 1 MB of compressed bytes (the first ones meet most gene names).
+// Every block's CRC-32 is checked on the device (the wave that inflated it reads it back).  Falls back to the host reader (returns false before anything was added) when
+// the configuration needs what the kernels do not do: -r parameter files, gene = chromosome name.
+// A sharded container is fed the same way: ONE decoder, on the GPU of the shard the file's first read goes to and on that shard's stream, for the
+// whole file (the record cut off at a window's end waits inside it); the container cuts every window at its quota boundaries and appends the
+// pieces to the shards' resident reads, device to device.
+#include "bam_parse.h"
+#include "../../../include/dropest_bgzf.h"
+#include "../../../include/dropest_annotation.h"
+
+#include <fcntl.h>
+#include <sys/mman.h>
+#include <sys/stat.h>
+
+#include <atomic>
+
+namespace Estimation {
+namespace BamProcessing {
+
+namespace {
+std::mutex &decoder_cache_mutex() { static std::mutex m; return m; }
+std::unordered_map<int, dropest_bam_decoder *> &decoder_cache() { static auto *c = new std::unordered_map<int, dropest_bam_decoder *>(); return *c; }   // (never destroyed: the HIP runtime may be gone by then)
+// The decoders of the files just read go back on a helper thread (several GB of device buffers and up to 512 MB of pinned staging: ~40 ms of
+// hipFree / hipHostFree that the container's passes need not wait for).  Joined before the next file list, by release_device_decoders(), and
+// at exit before the HIP runtime goes down (std::atexit handlers run in reverse order of registration, and the runtime registered first).
+std::thread *&release_thread() { static std::thread *t = nullptr; return t; }
+}  // namespace
+
+void join_release_thread() {
+	std::thread *t = nullptr;
+	{ std::lock_guard<std::mutex> lk(decoder_cache_mutex()); t = release_thread(); release_thread() = nullptr; }
+	if (t) { if (t->joinable()) t->join(); delete t; }
+}
+void release_decoders_in_background() {
+	join_release_thread();
+	std::lock_guard<std::mutex> lk(decoder_cache_mutex());
+	if (decoder_cache().empty()) return;
+	std::vector<dropest_bam_decoder *> gone;
+	for (auto &kv : decoder_cache()) gone.push_back(kv.second);
+	decoder_cache().clear();
+	static const bool at_exit = (std::atexit(join_release_thread), true);
+	(void)at_exit;
+	release_thread() = new std::thread([gone] { for (dropest_bam_decoder *d : gone) dropest_bam_decoder_destroy(d); });
+}
+
+void BamController::release_device_decoders() {
+	join_release_thread();
+	std::lock_guard<std::mutex> lk(decoder_cache_mutex());
+	for (auto &kv : decoder_cache()) dropest_bam_decoder_destroy(kv.second);
+	decoder_cache().clear();
+}
+
+namespace {
+
+int host_inflate(const uint8_t *in, uint32_t in_len, uint8_t *out_bytes, uint32_t out_len, void *) {
+	RawBlock b; b.cdata = in; b.clen = in_len; b.isize = out_len; b.crc = le32(in + in_len);
+	try { inflate_block(b, out_bytes); } catch (...) { return 1; }
+	return 0;
+}
+
+// (d) How large the windows of one file are: pure arithmetic over the file's size, its first blocks and the switches.
+struct WindowPlan {
+	size_t window_max = 0, window_blocks = 0, block_cap = 0, stage_cap = 0;
+	size_t inflated_seen = 0, compressed_seen = 0;      // over the first 64 blocks behind the header: how far this file inflates
+	size_t avg_block = size_t(1) << 14;
+	uint32_t n_pieces = 0;
+};
+WindowPlan plan_windows(const BamSwitches &sw, const uint8_t *p, size_t n, size_t c0, size_t wave_slots) {
+	WindowPlan w;
+	// windows: a machine's worth of blocks (one wave per block) in a file of a few hundred MB, two in a long one (measured on 0.4 and 1.6 GB:
+	// NOTES_r05 §11) -- the pinned staging buffers of larger windows cost more to allocate than their fuller kernels give back
+	const bool long_file = n > (size_t(1) << 30);
+	w.window_max = (sw.has_window_mb ? sw.window_mb : size_t(long_file ? 80 : 48)) << 20;
+	// (DROPEST_BAM_WINDOW_BLOCKS: blocks per window instead of the device's wave slots, twice that in a long file)
+	w.window_blocks = sw.has_window_blocks ? sw.window_blocks : std::max<size_t>(1024, wave_slots) * (long_file ? 2 : 1);
+	if (!sw.has_window_mb) {
+		// ... of blocks, not of bytes: a file that deflates 3 x (real bases and qualities) has blocks of ~20 KB where the 10 x synthetic ones have 6 KB,
+		// and a window of 48 MB of them would fill a third of the wave slots -- each window takes the time of ONE block however many it holds.
+		// The blocks behind the header say how large they are; up to 128 / 256 MB of staging (9.5 ms of pinning per 48 MB: NOTES_r05 section 13).
+		// (the laxest walk: two magic bytes, and a BC subfield may end beyond XLEN)
+		size_t at = c0, n_seen = 0, bytes_seen = 0;
+		while (n_seen < 64 && at + 18 <= n && p[at] == 31 && p[at + 1] == 139) {
+			const size_t bsize = bgzf::parse_header(p + at, n - at).bsize_cut;
+			if (!bsize || at + bsize > n) break;
+			w.inflated_seen += le32(p + at + bsize - 4);
+			at += bsize; bytes_seen += bsize; ++n_seen;
+		}
+		w.compressed_seen = bytes_seen;
+		if (n_seen >= 8) {
+			const size_t want = w.window_blocks * (bytes_seen / n_seen + 1);
+			w.window_max = std::min(std::max(w.window_max, want), size_t(sw.has_window_blocks ? 512 : long_file ? 256 : 128) << 20);
+			w.window_max = std::min(w.window_max, std::max<size_t>(n - c0, size_t(1) << 20));      // (no more than the file)
+		}
+	}
+	w.stage_cap = w.window_max + (size_t(1) << 17);
+	w.block_cap = sw.has_window_mb ? size_t(-1) : w.window_blocks;   // (one wave per block: a full machine's worth per window)
+	w.avg_block = w.compressed_seen >= 64 ? std::max<size_t>(w.compressed_seen / 64, 64) : size_t(1) << 14;
+	// (the copy out of the page cache runs at ~4-5 GB/s per thread; a piece being sent, one being filled, per reader)
+	w.n_pieces = 2 * sw.readers;
+	return w;
+}
+
+struct Staged { const uint8_t *p = nullptr; size_t used = 0; bool final = false; std::string error; };
+
+// One file through the device.  Lives for the file; the members are destroyed in reverse order: the window reader is waited for first, the
+// annotation goes, the decoder's lent stream is given back and the decoder cached or destroyed, the file unmapped last.
+class DeviceFileReader {
+	FileIngest &file;
+	const BamSwitches &sw;
+	CellsDataContainer &container;
+	const RecordParser &parser;
+	const CellsDataContainer::IngestTarget target;
+	const clk::time_point t_enter;
+	clk::time_point t_file;
+	struct Map {
+		const BamSwitches &sw;
+		const uint8_t *p = nullptr; size_t n = 0; int fd = -1;
+		~Map() {
+			const auto t = clk::now();
+			if (p) munmap(const_cast<uint8_t *>(p), n);
+			if (fd >= 0) close(fd);
+			sw.trace("[bam] device path: file unmapped %.1f ms\n", since(t));
+		}
+	} map;
+	struct Keep {    // back into the cache when the file went through, destroyed when it did not (whatever state an exception left)
+		const BamSwitches &sw;
+		dropest_bam_decoder *d = nullptr; int device = 0; bool ok = false;
+		~Keep() {
+			if (!d) return;
+			const auto t_k = clk::now();
+			(void)dropest_bam_decoder_use_stream(d, nullptr);      // (the container's stream is the container's)
+			sw.trace("[bam] device path: the lent stream given back (and waited for) %.1f ms\n", since(t_k));
+			if (!ok) { dropest_bam_decoder_destroy(d); return; }
+			std::lock_guard<std::mutex> lk(decoder_cache_mutex());
+			auto &slot = decoder_cache()[device];
+			if (slot) dropest_bam_decoder_destroy(slot);
+			slot = d;
+		}
+	} keep_dec;
+	dropest_bam_decoder *dec = nullptr;
+	// -g: the annotation's flat tables on the device (annotation_api.hip); the decoder asks it about the two ends of every alignment
+	struct FreeAnn { dropest_annotation *a = nullptr; ~FreeAnn() { if (a) dropest_annotation_destroy(a); } } ann;
+	Tools::GeneAnnotation::RefGenesContainer::Flat flat;
+	std::vector<uint64_t> ann_gene_hash;
+	std::vector<int32_t> id_of_ann_gene;
+	size_t c0 = 0; uint32_t u0 = 0;      // where the records begin: the block's file offset, the bytes of the header inside it
+	WindowPlan plan;
+	std::vector<uint32_t> idx_all, offsets, p_pos, p_gene, p_aux; std::vector<uint64_t> need_off, p_cb, p_umi; std::vector<uint8_t> need_bytes;
+	std::vector<uint64_t> dict_hash; std::vector<uint32_t> dict_id; std::vector<int32_t> dict_chr;
+	std::vector<uint32_t> name_off; std::vector<uint8_t> name_pool;
+	double dev_ms[4] = {0, 0, 0, 0}, host_ms[3] = {0, 0, 0};
+	double ms_header = 0, ms_create = 0, ms_setup = 0, ms_wait_read = 0, ms_window_calls = 0;
+	size_t window_bytes = 0, n_windows = 0, repaired = 0, refused = 0, n_needs = 0, est_reads = 0;
+	bool first = true, dict_dirty = true;
+	int which = 0;
+	// the window reader's (a helper thread at a time): where the next window begins, the staging memory, the block tables
+	size_t file_at = 0;
+	uint8_t *stage_p[2] = {nullptr, nullptr};
+	uint8_t *piece_p[16] = {};
+	bgzf::Blocks blocks_of[2];
+	std::atomic<size_t> stretched_windows{0};
+	std::future<Staged> next;
+	struct Drain { std::future<Staged> &f; ~Drain() { if (f.valid()) f.wait(); } };   // (an exception must not leave the reader running on freed buffers)
+
+	[[noreturn]] void fail() const { throw std::runtime_error(std::string(dropest_bgzf_last_error()) + ": " + file.bam_name); }
+
+	bool open_file();
+	void read_header();
+	bool lease_decoder();
+	bool annotation_to_device();
+	void staging();
+	Staged read_window(int which, size_t want);
+	Staged read_window_in_pieces(int which, size_t want, size_t ask);
+	Staged read_whole_window(int which, size_t want, size_t ask);
+	void read_next() { const int k = which; const size_t want = window_bytes; next = std::async(std::launch::async, [this, k, want] { return read_window(k, want); }); }
+	// the ramp goes on and the buffers change places; the window after `stg` is read meanwhile
+	void next_window_after(bool last) { window_bytes = std::min(window_bytes * sw.ramp_factor, plan.window_max); which ^= 1; if (!last) read_next(); }
+	Staged wait_for_window(std::future<Staged> &f) {
+		const auto t_wait = clk::now();
+		Staged stg = f.get();
+		ms_wait_read += since(t_wait);
+		if (!stg.error.empty()) throw std::runtime_error(stg.error + ": " + file.bam_name);
+		return stg;
+	}
+	void dictionaries_to_device();
+	void take_window(const dropest_bam_window &w, size_t used, clk::time_point t_call);
+	void records_through_host(const dropest_bam_window &w, size_t n);
+	void resolve_new(const dropest_bam_window &w);
+	void windows_one_by_one();
+	void windows_pipelined();
+public:
+	DeviceFileReader(FileIngest &file, CellsDataContainer::IngestTarget target, clk::time_point t_enter)
+		: file(file), sw(file.sw), container(file.container), parser(file.parser), target(target), t_enter(t_enter), map{file.sw}, keep_dec{file.sw} {}
+	bool read();
+};
+
+// (a) the file mapped; false: the host reader says what is wrong with it
+bool DeviceFileReader::open_file() {
+	map.fd = open(file.bam_name.c_str(), O_RDONLY);
+	if (map.fd < 0) return false;
+	struct stat sb;
+	if (fstat(map.fd, &sb) || sb.st_size <= 0) return false;
+	map.n = size_t(sb.st_size);
+	void *mp = mmap(nullptr, map.n, PROT_READ, MAP_PRIVATE, map.fd, 0);
+	if (mp == MAP_FAILED) return false;
+	map.p = static_cast<const uint8_t *>(mp);
+	// (the mapping is read at every block's header only, a cache line per ~20 KB: without this every fault maps its 16 neighbours too, and
+	// half a million page-table entries of a 683 MB file took 38 ms to unmap)
+	(void)madvise(mp, map.n, MADV_RANDOM);
+	return true;
+}
+
+// (a) where the records begin: magic, l_text, text, n_ref, (l_name, name, l_ref) x n_ref -- blocks inflated here until that much is seen
+void DeviceFileReader::read_header() {
+	const std::string &bam_name = file.bam_name;
+	std::vector<std::string> &refs = file.refs;
+	size_t at = 0;
+	std::vector<uint8_t> hdr;
+	std::vector<std::pair<size_t, size_t>> starts;   // (file offset of the block, inflated bytes before it)
+	auto have = [&](size_t nbytes) {
+		while (hdr.size() < nbytes) {
+			RawBlock b;
+			const size_t before = at;
+			if (!read_block(map.p, map.n, at, b, bam_name)) throw std::runtime_error("Truncated BAM header: " + bam_name);
+			starts.emplace_back(before, hdr.size());
+			hdr.resize(hdr.size() + b.isize);
+			inflate_block(b, hdr.data() + hdr.size() - b.isize);
+		}
+	};
+	have(12);
+	if (std::memcmp(hdr.data(), "BAM\1", 4) != 0) throw std::runtime_error("Can't open BAM file: " + bam_name);
+	size_t h = 8 + size_t(le32(hdr.data() + 4));
+	have(h + 4);
+	const uint32_t n_ref = le32(hdr.data() + h);
+	h += 4;
+	refs.clear();
+	for (uint32_t r = 0; r < n_ref; ++r) {
+		have(h + 4);
+		const size_t ln = le32(hdr.data() + h);
+		have(h + 4 + ln + 4);
+		refs.emplace_back(reinterpret_cast<const char *>(hdr.data() + h + 4), ln ? ln - 1 : 0);
+		h += 4 + ln + 4;
+	}
+	container.set_reference_names(refs);
+	c0 = at; u0 = 0;                                 // the header ends with a block: the records open the next one
+	for (size_t k = starts.size(); k-- > 0;)
+		if (starts[k].second <= h && h < (k + 1 < starts.size() ? starts[k + 1].second : hdr.size())) { c0 = starts[k].first; u0 = uint32_t(h - starts[k].second); break; }
+}
+
+// (b) One decoder per device is kept between the files of one parse_bam_files call (streams, device buffers of ~15 x the staging size --
+// 2 to 7 GB for windows of 128 to 256 MB -- and 2 x 32 to 2 x 256 MB of pinned staging: ~30 ms to set up, ~40 ms to give back); after the
+// last file they are given back on a helper thread (release_decoders_in_background) unless DROPEST_BAM_KEEP_DECODERS=1 keeps them
+// for the next call of a long-lived process.
+bool DeviceFileReader::lease_decoder() {
+	const BamTags &tags = parser.tags;
+	dropest_bam_parse_cfg cfg{};
+	for (int k = 0; k < 6; ++k) cfg.tag[k] = parser.wanted_tags[k];
+	cfg.filled_bam = parser.filled_bam ? 1 : 0; cfg.min_phred = parser.min_barcode_phred; cfg.has_read_type = tags.read_type.empty() ? 0 : 1;
+	cfg.n_refs = int32_t(file.refs.size());
+	cfg.intronic_len = uint32_t(tags.intronic_read_value.size()); cfg.intergenic_len = uint32_t(tags.intergenic_read_value.size());
+	std::memcpy(cfg.intronic, tags.intronic_read_value.data(), cfg.intronic_len);
+	std::memcpy(cfg.intergenic, tags.intergenic_read_value.data(), cfg.intergenic_len);
+	dropest_bam_decoder *d = nullptr;
+	{
+		std::lock_guard<std::mutex> lk(decoder_cache_mutex());
+		auto it = decoder_cache().find(target.device);
+		if (it != decoder_cache().end()) { d = it->second; decoder_cache().erase(it); }
+	}
+	if (d && dropest_bam_decoder_reset(d, &cfg)) { dropest_bam_decoder_destroy(d); d = nullptr; }
+	if (!d && dropest_bam_decoder_create(target.device, &cfg, &d)) return false;       // (no GPU for this: the host reader does it)
+	// its kernels on the container's stream (a sharded one: that shard's) for this file: that one exists and has run kernels; one of the decoder's own is ~16 ms to make
+	if (target.stream && dropest_bam_decoder_use_stream(d, target.stream)) { dropest_bam_decoder_destroy(d); return false; }
+	dec = keep_dec.d = d; keep_dec.device = target.device;
+	return true;
+}
+
+// (c) -g: the annotation's tables; false: positions beyond 32 bits, or no room for them (the host reader does it)
+bool DeviceFileReader::annotation_to_device() {
+	const std::vector<std::string> &refs = file.refs;
+	if (parser.genes.is_empty()) return true;
+	try { flat = parser.genes.flatten(); } catch (const std::exception &) { return false; }   // (positions beyond 32 bits: the host reader does it)
+	dropest_flat_annotation fa{};
+	fa.n_chr = uint32_t(flat.chr_names.size()); fa.n_seg = uint32_t(flat.seg_start.size()); fa.n_tr = uint32_t(flat.tr_gene.size()); fa.n_genes = uint32_t(flat.gene_names.size());
+	fa.use_introns_from_gtf = flat.use_introns_from_gtf ? 1 : 0;
+	fa.chr_seg_begin = flat.chr_seg_begin.data(); fa.seg_start = flat.seg_start.data(); fa.seg_end = flat.seg_end.data(); fa.seg_tr_begin = flat.seg_tr_begin.data();
+	fa.seg_tr = flat.seg_tr.data(); fa.tr_gene = flat.tr_gene.data(); fa.tr_exon_begin = flat.tr_exon_begin.data(); fa.tr_intron_begin = flat.tr_intron_begin.data();
+	fa.exon_start = flat.exon_start.data(); fa.exon_end = flat.exon_end.data(); fa.intron_start = flat.intron_start.data(); fa.intron_end = flat.intron_end.data();
+	if (dropest_annotation_create(target.device, &fa, &ann.a)) return false;
+	std::unordered_map<std::string, int32_t> chr_index;
+	for (size_t k = 0; k < flat.chr_names.size(); ++k) chr_index.emplace(flat.chr_names[k], int32_t(k));
+	std::vector<int32_t> ann_chr_of_ref(refs.size(), -1);
+	for (size_t r = 0; r < refs.size(); ++r) { auto it = chr_index.find(refs[r]); if (it != chr_index.end()) ann_chr_of_ref[r] = it->second; }
+	if (dropest_bam_decoder_set_annotation(dec, ann.a, ann_chr_of_ref.data(), uint32_t(refs.size()))) fail();
+	ann_gene_hash.resize(flat.gene_names.size());
+	for (size_t g = 0; g < flat.gene_names.size(); ++g) ann_gene_hash[g] = CellsDataContainer::hash_name(flat.gene_names[g]);
+	id_of_ann_gene.assign(flat.gene_names.size(), -1);
+	return true;
+}
+
+// The compressed bytes reach the device in pieces: helper threads (up to eight for a long window) read the next window from the file into
+// pinned pieces of 2 MB (pread: page cache -> pinned memory) and sends each on its way (dropest_bam_decoder_upload_piece) while the device
+// and this thread work on the window before.  The window itself is the mapped file's bytes: the block table is made from them, the host
+// fall-back for a refused block reads them.  (Rounds 4-6a read whole windows into two pinned buffers of the window's size: 2 x 128 MB were
+// 35-65 ms to allocate, a fifth to a third of a 16 M read file's time -- DROPEST_BAM_WHOLE_WINDOW_STAGING=1 takes that road.)
+void DeviceFileReader::staging() {
+	const size_t stage_cap = plan.stage_cap;
+	if (sw.in_pieces) {
+		for (int k = 0; k < 2; ++k)      // (first: the upload stream is made beside the pinned allocation, and a device allocation would wait for it)
+			if (dropest_bam_decoder_reserve(dec, k, stage_cap, plan.compressed_seen ? uint64_t(double(stage_cap) * double(plan.inflated_seen) / double(plan.compressed_seen) * 1.25) : 0)) fail();
+		sw.trace("[bam] device path: the device buffers of two windows of %zu MB %.1f ms\n", stage_cap >> 20, since(t_file));
+		if (dropest_bam_decoder_pieces(dec, plan.n_pieces, sw.piece_bytes, piece_p)) fail();
+		sw.trace("[bam] device path: ... and %u pinned pieces of %zu MB %.1f ms\n", plan.n_pieces, sw.piece_bytes >> 20, since(t_file));
+	} else
+		for (int k = 0; k < 2; ++k)      // (pinning 2 x 80 MB and reserving a window's device buffers: 35-50 ms; side by side on two threads they take as long)
+			if (dropest_bam_decoder_staging(dec, k, stage_cap, &stage_p[k])) fail();
+}
+
+// (e) the next window of the file into staging buffer `which`: up to `want` bytes of whole blocks.  Runs on a helper thread, one at a time.
+Staged DeviceFileReader::read_window(int which, size_t want) {
+	const size_t ask = std::min(std::min(want + (size_t(1) << 16) + 64, plan.stage_cap), map.n - file_at);
+	return sw.in_pieces ? read_window_in_pieces(which, want, ask) : read_whole_window(which, want, ask);
+}
+
+// the window's bytes to the device piece by piece (helper threads: everything up to `want` needs no block boundary), its extent and
+// block table from the file meanwhile (this thread), the last blocks' bytes beyond `want` at the end
+Staged DeviceFileReader::read_window_in_pieces(int which, size_t want, size_t ask) {
+	Staged st;
+	st.p = map.p + file_at;
+	bgzf::Blocks &B = blocks_of[which];
+	const size_t PIECE = sw.piece_bytes, at = file_at;
+	const int fd = map.fd;
+	const auto t_rw = clk::now();
+	struct SayRw { const BamSwitches &sw; clk::time_point t; size_t &used; ~SayRw() { sw.trace_reader("[bam] reader: a window of %.1f MB read and sent in %.2f ms\n", double(used) / 1048576.0, since(t)); } } say_rw{sw, t_rw, st.used};
+	std::atomic<bool> failed{dropest_bam_decoder_upload_begin(dec, which) != 0};
+	const size_t covered = std::min(want, ask);
+	const size_t n_pieces = (covered + PIECE - 1) / PIECE;
+	const uint32_t n_readers = uint32_t(std::min<size_t>(sw.readers, n_pieces));
+	const bool trace_rw = sw.trace_reader_on && file_at == c0;
+	auto lap_rw = [trace_rw, t_rw](const char *what) { if (trace_rw) std::fprintf(stderr, "[bam] reader, first window: %s at %.2f ms\n", what, since(t_rw)); };
+	lap_rw("upload_begin done");
+	dropest_bam_decoder *const d = dec;
+	uint8_t *const *const pieces = piece_p;
+	auto send = [d, pieces, fd, at, which, &failed, lap_rw](uint32_t slot, size_t from, size_t len) {
+		if (dropest_bam_decoder_piece_wait(d, slot)) { failed = true; return; }
+		lap_rw("piece_wait done");
+		size_t g = 0;
+		while (g < len) {
+			const ssize_t got = pread(fd, pieces[slot] + g, len - g, off_t(at + from + g));
+			if (got <= 0) { failed = true; return; }
+			g += size_t(got);
+		}
+		lap_rw("pread done");
+		if (dropest_bam_decoder_upload_piece(d, which, slot, from, len)) failed = true;
+		lap_rw("upload_piece done");
+	};
+	auto reader = [&send, &failed, n_pieces, n_readers, PIECE, covered](uint32_t r) {
+		for (size_t k = r, turn = 0; k < n_pieces && !failed.load(std::memory_order_relaxed); k += n_readers, ++turn)
+			send(2u * r + uint32_t(turn & 1u), k * PIECE, std::min(PIECE, covered - k * PIECE));
+	};
+	std::vector<std::future<void>> helpers;
+	for (uint32_t r = 0; r < n_readers; ++r) helpers.push_back(std::async(std::launch::async, reader, r));
+	bgzf::FileWalk walk;
+	walk.fd = fd; walk.file_at = at; walk.block_cap = plan.block_cap; walk.avg_block = plan.avg_block;
+	walk.least_bytes = sw.stretch_bytes; walk.least_blocks = sw.stretch_blocks; walk.one_walker = sw.one_walker;
+	bool stretched = false;
+	const size_t o = walk.whole_blocks_of_file(ask, want, B, st.error, &stretched);
+	if (stretched) ++stretched_windows;
+	lap_rw("block walk done");
+	for (auto &f : helpers) f.get();
+	lap_rw("helpers joined");
+	if (!st.error.empty()) return st;
+	for (size_t from = covered; from < o && !failed.load(); from += PIECE) send(0, from, std::min(PIECE, o - from));      // (at most 64 KB)
+	st.used = o; file_at += o; st.final = file_at >= map.n;
+	// (a piece that could not be read or sent: nothing is declared, and the window call copies the mapped bytes itself)
+	const dropest_bgzf_blocks table{uint64_t(B.in_off.size()), B.in_off.data(), B.in_len.data(), B.out_len.data(), B.crc.data()};
+	if (!failed.load()) (void)dropest_bam_decoder_upload_done(dec, which, st.p, o, &table);
+	lap_rw("upload_done done");
+	return st;
+}
+
+// the window read whole into pinned buffer `which` (DROPEST_BAM_WHOLE_WINDOW_STAGING, DROPEST_BAM_NO_UPLOAD_AHEAD)
+Staged DeviceFileReader::read_whole_window(int which, size_t want, size_t ask) {
+	Staged st;
+	uint8_t *const buf = stage_p[which];
+	st.p = buf;
+	const int fd = map.fd;
+	const size_t at = file_at;
+	// (the copy out of the page cache runs at ~4-5 GB/s per thread: a long window is read in four pieces side by side, so that the reader
+	// stays ahead of the device -- which takes ~11 ms per 64 MB window)
+	auto read_piece = [buf, fd, at](size_t from, size_t len) -> long {
+		size_t g = 0;
+		while (g < len) {
+			const ssize_t r = pread(fd, buf + from + g, len - g, off_t(at + from + g));
+			if (r < 0) return -1;
+			if (r == 0) break;
+			g += size_t(r);
+		}
+		return long(g);
+	};
+	size_t got = 0;
+	const size_t n_pieces = ask > (size_t(8) << 20) ? 4 : 1, piece = (ask / n_pieces + 4095) & ~size_t(4095);
+	std::vector<std::future<long>> rest;
+	for (size_t k = 1; k < n_pieces; ++k) if (k * piece < ask) rest.push_back(std::async(std::launch::async, read_piece, k * piece, std::min(piece, ask - k * piece)));
+	const long g0 = read_piece(0, std::min(piece, ask));
+	bool whole = g0 == long(std::min(piece, ask)), failed = g0 < 0;
+	if (g0 > 0) got = size_t(g0);
+	for (size_t k = 0; k < rest.size(); ++k) {
+		const long g = rest[k].get();
+		if (g < 0) failed = true;
+		else if (whole) { got += size_t(g); whole = size_t(g) == std::min(piece, ask - (k + 1) * piece); }
+	}
+	if (failed) { st.error = "Can't read BAM file"; return st; }
+	const size_t o = bgzf::whole_blocks(buf, got, want, plan.block_cap, st.error);
+	if (!st.error.empty()) return st;
+	st.used = o; file_at += o; st.final = file_at >= map.n;
+	if (sw.upload_ahead) (void)dropest_bam_decoder_upload(dec, which, o);   // on its way while the window before it is in the kernels (if this fails, the window call copies)
+	return st;
+}
+
+// (f) the dictionaries as they stand (other files, earlier windows, add_record calls) go to the device
+void DeviceFileReader::dictionaries_to_device() {
+	const auto t_phase = clk::now();
+	if (dict_dirty) {
+		container.dictionary_snapshot(dict_hash, dict_id, dict_chr);
+		if (dropest_bam_decoder_set_dictionaries(dec, dict_hash.data(), dict_id.data(), uint32_t(dict_hash.size()), dict_chr.data(), uint32_t(dict_chr.size()))) fail();
+		{   // ... and the genes' names: a hash the device finds is confirmed byte by byte (two names with one FNV-1a value must not share an index)
+			const auto &names = container.gene_indexer().values();
+			name_off.resize(names.size() + 1);
+			size_t bytes = 0;
+			for (size_t g = 0; g < names.size(); ++g) { name_off[g] = uint32_t(bytes); bytes += names[g].size(); }
+			name_off[names.size()] = uint32_t(bytes);
+			name_pool.resize(bytes + 1);
+			for (size_t g = 0; g < names.size(); ++g) std::memcpy(name_pool.data() + name_off[g], names[g].data(), names[g].size());
+			if (bytes > 0xFFFFFFF0ull || dropest_bam_decoder_set_gene_names(dec, name_off.data(), name_pool.data(), uint32_t(names.size()))) fail();
+		}
+		if (ann.a) {   // the annotation's genes that the dictionary holds by now
+			for (size_t g = 0; g < flat.gene_names.size(); ++g)
+				if (id_of_ann_gene[g] < 0) id_of_ann_gene[g] = int32_t(container.lookup_gene(ann_gene_hash[g], flat.gene_names[g]));
+			if (dropest_bam_decoder_set_annotation_genes(dec, id_of_ann_gene.data(), uint32_t(id_of_ann_gene.size()))) fail();
+		}
+		dict_dirty = false;
+	}
+	host_ms[0] += since(t_phase);
+}
+
+// (g) UMI quality strings the container cannot take in bulk (it keeps them on the host): the records of this window come back as bytes and
+// take the host reader's bulk path over them (BulkWindow: one quality row per read while the strings have one length), or, where that
+// refuses, go record by record
+void DeviceFileReader::records_through_host(const dropest_bam_window &w, size_t n) {
+	idx_all.resize(n); need_off.resize(n);
+	for (size_t i = 0; i < n; ++i) idx_all[i] = uint32_t(i);
+	need_bytes.resize(size_t(w.window_bytes) + 16);
+	if (dropest_bam_decoder_fetch_records(dec, idx_all.data(), uint32_t(n), need_bytes.data(), need_bytes.size(), need_off.data())) fail();
+	offsets.resize(n);
+	for (size_t i = 0; i < n; ++i) offsets[i] = uint32_t(need_off[i]);
+	dict_dirty = true;
+	if (w.window_bytes < (uint64_t(1) << 32) && !sw.record_by_record && container.bulk_ingest_possible_at_all() && file.bulk.ingest(need_bytes.data(), offsets, n)) return;
+	Parsed tmp;
+	for (size_t i = 0; i < n; ++i) {
+		parser.parse(need_bytes.data() + need_off[i], tmp);
+		if (count_status(file.counters, tmp.status)) container.add_record(tmp.r);
+	}
+}
+
+// (g) what the dictionaries have not seen, in file order: the records that bring it come back as bytes, their columns are patched on the device
+void DeviceFileReader::resolve_new(const dropest_bam_window &w) {
+	const size_t m = w.n_need;
+	n_needs += m;
+	size_t bytes = 0;
+	for (size_t k = 0; k < m; ++k) bytes += w.need_size[k];
+	need_bytes.resize(bytes + 16); need_off.resize(m);
+	p_pos.resize(m); p_cb.resize(m); p_umi.resize(m); p_gene.resize(m); p_aux.resize(m);
+	if (dropest_bam_decoder_fetch_records(dec, w.need_rec, uint32_t(m), need_bytes.data(), need_bytes.size(), need_off.data())) fail();
+	Parsed tmp;
+	for (size_t k = 0; k < m; ++k) {
+		parser.parse(need_bytes.data() + need_off[k], tmp);
+		if (tmp.status != Parsed::OK) throw std::runtime_error("internal: the device and the host read a BAM record differently: " + file.bam_name);
+		const CellsDataContainer::ParsedRead &r = tmp.r;
+		const bool has_gene = !r.gene.empty();
+		const bool touches = !has_gene || (r.mark & (UMI::Mark::HAS_EXONS | UMI::Mark::HAS_INTRONS));
+		// (a gene and a chromosome are entered whether the dictionaries know them or not: they then answer with what they hold)
+		const uint8_t what = uint8_t((r.cb_code ? 0 : NEED_CB) | (has_gene && !r.umi_code ? NEED_UMI : 0) | (has_gene ? NEED_GENE : 0) | (touches ? NEED_CHR : 0));
+		p_pos[k] = w.need_pos[k];
+		p_cb[k] = r.cb_code; p_umi[k] = has_gene ? r.umi_code : 1; p_gene[k] = DROPEST_NO_GENE; p_aux[k] = uint32_t(r.mark) << 16;
+		intern_new(container, NewParts{what, r.ref_id, r.cb, r.umi, r.gene, r.gene_hash}, p_cb[k], p_umi[k], p_gene[k], p_aux[k]);
+	}
+	if (dropest_bam_decoder_patch(dec, p_pos.data(), p_cb.data(), p_umi.data(), p_gene.data(), p_aux.data(), uint32_t(m))) fail();
+	dict_dirty = true;
+}
+
+// (g) one decoded window into the container and the counters
+void DeviceFileReader::take_window(const dropest_bam_window &w, size_t used, clk::time_point t_call) {
+	ms_window_calls += since(t_call);
+	if (first) {
+		est_reads = size_t(double(w.n_records) * double(map.n - c0) / double(std::max<size_t>(used, 1)) * double(file.n_files) * 1.05);
+		const auto t_e = clk::now();
+		container.expect_reads(est_reads);
+		sw.trace("[bam] device path: the container told to expect %zu reads %.1f ms\n", est_reads, since(t_e));
+	}
+	first = false;
+	++n_windows; repaired += w.guesses_repaired; refused += w.refused_blocks;
+	dev_ms[0] += w.ms_copy; dev_ms[1] += w.ms_inflate; dev_ms[2] += w.ms_boundaries; dev_ms[3] += w.ms_parse;
+	sw.trace_reader("[bam] window %zu: %.1f MB, %u blocks, %llu records: copy in %.2f, inflate %.2f, chain %.2f, fields %.2f ms; the call %.2f ms\n", n_windows, double(used) / 1048576.0, w.n_blocks, (unsigned long long)w.n_records, w.ms_copy, w.ms_inflate, w.ms_boundaries, w.ms_parse, since(t_call));
+	const size_t n = size_t(w.n_records);
+	if (!n) return;
+	auto t_phase = clk::now();
+	// UMI quality strings: one length over the gene-bearing reads of the window (and the container's so far) -> the device hands over one row
+	// per accepted read beside the columns; anything else -> the window's records come back as bytes
+	const bool has_q = w.any_gene && w.quality_len_max > 0;
+	const uint32_t q_len = w.quality_len_max;
+	const bool q_bulk = has_q && w.quality_len_min == w.quality_len_max && container.bulk_ingest_possible_with_quality(q_len, true);
+	if (has_q ? !q_bulk : !container.bulk_ingest_possible(true)) {
+		records_through_host(w, n);
+		host_ms[1] += since(t_phase);
+		return;
+	}
+	if (w.n_need) resolve_new(w);
+	host_ms[1] += since(t_phase); t_phase = clk::now();
+	bool any_gene = w.any_gene != 0;
+	for (size_t k = 0; k < size_t(w.n_need) && !any_gene; ++k) any_gene = p_gene[k] != DROPEST_NO_GENE;
+	if (q_bulk) {
+		container.reserve_quality_rows(est_reads, q_len);
+		const uint8_t *rows = nullptr;
+		if (dropest_bam_decoder_quality_rows(dec, q_len, &rows)) fail();
+		container.add_records_packed_device(w.d_cb, w.d_umi, w.d_gene, w.d_aux, size_t(w.n_accepted), any_gene, rows, q_len, target.device, target.stream);
+	} else
+		container.add_records_packed_device(w.d_cb, w.d_umi, w.d_gene, w.d_aux, size_t(w.n_accepted), any_gene, target.device, target.stream);
+	host_ms[2] += since(t_phase);
+	BamController::Counters &c = file.counters;
+	c.cant_parse += size_t(w.counts[DROPEST_BAM_CANT_PARSE_NO_COUNT] + w.counts[DROPEST_BAM_CANT_PARSE]);
+	c.low_quality += size_t(w.counts[DROPEST_BAM_LOW_QUALITY]);
+	c.saved += size_t(w.counts[DROPEST_BAM_OK]);
+	c.total_reads += size_t(w.counts[DROPEST_BAM_OK] + w.counts[DROPEST_BAM_CANT_PARSE] + w.counts[DROPEST_BAM_LOW_QUALITY]);
+}
+
+// (h) the default order: window k is through the device and the container before window k + 1 (read meanwhile) is given to the device
+void DeviceFileReader::windows_one_by_one() {
+	for (;;) {
+		const Staged stg = wait_for_window(next);
+		next_window_after(stg.final);
+		Drain drain{next};
+		dictionaries_to_device();
+		dropest_bam_window w{};
+		const auto t_call = clk::now();
+		if (dropest_bam_decoder_window(dec, stg.p, stg.used, first ? u0 : 0u, stg.final ? 1 : 0, host_inflate, nullptr, &w)) fail();
+		take_window(w, stg.used, t_call);
+		if (stg.final) break;
+	}
+}
+
+// (h) Round 6, DROPEST_BAM_PIPELINE=1 (off by default): the inflate of window k + 1 is given to the device BEFORE this thread waits for window k
+// (dropest_bam_decoder_window_inflate / _chain).  A window's inflate lasts as long as its slowest block (7-11 ms on a file that deflates
+// 3 x) and one window after the other leaves wave slots empty -- 86 ms of inflate in situ for a kernel that needs 42
+// (profiles/r06a_bam_3x_file_device_trace.txt) -- but the next window's blocks then hold every slot while this window's small kernels
+// and copies want some: inside the window calls 109-121 -> 81-95 ms, the dictionaries' copies 1 -> 31 ms, two more streams to create
+// (8 ms each): ingest 195 -> 233 ms on the same box.  Kept as an order the library supports and the suite runs; not the default.
+void DeviceFileReader::windows_pipelined() {
+	Staged stg = wait_for_window(next), stg_ahead;
+	int slot_cur = 0, slot_ahead = 0;
+	next_window_after(stg.final);
+	if (dropest_bam_decoder_window_inflate(dec, stg.p, stg.used, &slot_cur)) { if (next.valid()) next.wait(); fail(); }
+	for (;;) {
+		const bool final = stg.final;
+		Drain drain{next};
+		if (!final) {      // the window after this one: read by now (its buffer is the other one), its blocks to the device
+			stg_ahead = wait_for_window(next);
+			const auto t_a = clk::now();
+			if (dropest_bam_decoder_window_inflate(dec, stg_ahead.p, stg_ahead.used, &slot_ahead)) fail();
+			ms_window_calls += since(t_a);
+		}
+		dictionaries_to_device();
+		dropest_bam_window w{};
+		const auto t_call = clk::now();
+		if (dropest_bam_decoder_window_chain(dec, slot_cur, first ? u0 : 0u, final ? 1 : 0, host_inflate, nullptr)) fail();
+		// this window's compressed bytes are done with: the reader may fill their buffer with the window after the next
+		if (!final && !stg_ahead.final) next_window_after(false);
+		if (dropest_bam_decoder_window_finish(dec, slot_cur, &w)) fail();
+		take_window(w, stg.used, t_call);
+		if (final) break;
+		stg = std::move(stg_ahead); slot_cur = slot_ahead;
+	}
+}
+
+bool DeviceFileReader::read() {
+	if (!open_file()) return false;
+	read_header();
+	ms_header = since(t_enter);
+	if (!lease_decoder()) return false;
+	ms_create = since(t_enter) - ms_header;
+	if (!annotation_to_device()) return false;
+	t_file = clk::now();
+	// (1 MB first: the file's genes and chromosomes are mostly met there, and every one of them is a record the host parses -- a first window of
+	// 4 / 8 / 16 MB: 65 -> 76 / 79 / 87 ms on the 3.2 x file; then x 8: 1, 8, 64 MB ... measured against x 4 and x 16 with the round's final decoder:
+	// 3.2 x file 65-70 -> 59-67 ms, 10.8 x file 85-87 -> 73-75)
+	window_bytes = sw.ramp_first << 20;
+	plan = plan_windows(sw, map.p, map.n, c0, dropest_bam_decoder_wave_slots(dec));
+	staging();
+	ms_setup = since(t_file);
+	file_at = c0;
+	read_next();
+	if (sw.pipeline) windows_pipelined(); else windows_one_by_one();
+	sw.trace("[bam] device path: %zu windows, %.1f ms behind the header; copy in %.1f ms, inflate %.1f ms (%zu blocks left to the host), record chain %.1f ms (%zu guesses "
+	         "repaired), fields + dense columns %.1f ms; host: dictionaries to the device %.1f ms, %zu records with something new %.1f ms, container %.1f ms\n",
+	         n_windows, since(t_file), dev_ms[0], dev_ms[1], refused, dev_ms[2], repaired, dev_ms[3], host_ms[0], n_needs, host_ms[1], host_ms[2]);
+	sw.trace("[bam] device path: file mapped and header read %.1f ms, decoder created %.1f ms, annotation + the rest before the windows %.1f ms\n", ms_header, ms_create, std::chrono::duration<double, std::milli>(t_file - t_enter).count() - ms_header - ms_create);
+	sw.trace("[bam] device path: pinned staging buffers %.1f ms, waiting for the file reader %.1f ms, inside the window calls %.1f ms\n", ms_setup, ms_wait_read, ms_window_calls);
+	keep_dec.ok = true;
+	sw.trace("[bam] device path: %.1f ms from the file's name to its last window (block tables from four stretches: %zu windows)\n", since(t_enter), stretched_windows.load());
+	return true;
+}
+
+}  // namespace
+
+bool read_file_on_device(FileIngest &file) {
+	const RecordParser &parser = file.parser;
+	if (parser.params_from_files || parser.gene_in_chromosome_name || !file.container.bulk_ingest_possible_at_all(true)) return false;
+	const CellsDataContainer::IngestTarget target = file.container.next_read_target();
+	const auto t_enter = clk::now();
+	if (parser.tags.intronic_read_value.size() > 24 || parser.tags.intergenic_read_value.size() > 24) return false;
+	DeviceFileReader reader(file, target, t_enter);
+	return reader.read();
+}
+
+}  // namespace BamProcessing
+}  // namespace Estimation

@@ -28,6 +28,9 @@
 namespace Estimation {
 namespace BamProcessing {
 
+struct Parsed;       // bam_parse.h: one record as the controller's parser read it
+struct FileIngest;   // bam_parse.h: what the readers of one file share
+
 struct BamTags {   // BamTags.cpp:7-24 (defaults of the XML config)
 	std::string cell_barcode = "CB", cell_barcode_raw = "CR", umi = "UB", umi_raw = "UR", gene = "GX";
 	std::string cell_barcode_quality = "CQ", umi_quality = "UQ";
@@ -84,6 +87,9 @@ private:
 	std::unordered_map<std::string, ReadParams> _read_params;     // -r: read name -> parameters (erased when served)
 	bool _params_from_files = false;
 	void load_read_params(const std::string &filenames);
+	void serve_read_params(Parsed &pr);
+	void add_record_by_record(FileIngest &file, const uint8_t *data, const std::vector<uint32_t> &offsets, std::vector<Parsed> &parsed);
+	void read_file_on_host(FileIngest &file, bool first_file);
 	bool _filled_bam, _gene_in_chromosome_name;
 	int _min_barcode_phred;
 	unsigned _threads;
@@ -97,8 +103,8 @@ public:
 	// BamController::parse_bam_files with a BamProcessor: every accepted read reaches container.add_record in file order
 	void parse_bam_files(const std::vector<std::string> &bam_files, CellsDataContainer &container);
 	// BGZF inflate, record chain and tag walk on the container's GPU (include/dropest_bgzf.h) where the configuration allows it: tags or read
-	// names as the source of barcode / UMI, the gene tag or a -g annotation (annotation_api.hip) as the source of the gene; not with -r, gene =
-	// chromosome name, or a sharded container (the host reader then runs).
+	// names as the source of barcode / UMI, the gene tag or a -g annotation (annotation_api.hip) as the source of the gene; not with -r or gene =
+	// chromosome name (the host reader then runs).  A sharded container is fed by one decoder on the GPU of the shard the file's first read goes to.
 	// CRC-32 and ISIZE of every block are checked there too.  DROPEST_BAM_DEVICE=1 in the environment does the same.
 	void set_device_decode(bool on) { _device_decode = on; }
 	// the device path keeps one decoder per GPU (streams, 2-7 GB of device buffers, up to 512 MB of pinned staging) between the files of one

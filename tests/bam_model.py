@@ -80,7 +80,7 @@ _WIDTH = {ord("A"): 1, ord("c"): 1, ord("C"): 1, ord("s"): 2, ord("S"): 2, ord("
 
 
 def string_tags(tags, wanted):
-    """BamRecord::get_string_tags (host/bam_ingest.cpp:571-610): one walk over the aux bytes.  Returns {k: value bytes} for the wanted names.
+    """BamRecord::get_string_tags (host/bam_ingest.cpp:474-513): one walk over the aux bytes.  Returns {k: value bytes} for the wanted names.
     - the first occurrence of a name wins;
     - Z and H are strings up to their NUL; A counts as a string of one byte;
     - any numeric occurrence (c C s S i I f, B) "closes" the name: later occurrences of it are not looked at;
@@ -170,7 +170,7 @@ def parse_record(rec, cfg, dicts):
         mark = HAS_EXONS
     gname = tv.get(T_GENE, b"")
     has_gene = len(gname) > 0                                             # an empty gene name is no gene
-    # the columns as fast_window (host/bam_ingest.cpp) fills them; 0 / need where the dictionaries cannot answer
+    # the columns as BulkWindow (host/bam_controller.cpp) fills them; 0 / need where the dictionaries cannot answer
     need = False
     cbc = pack(cb)
     need |= cbc == 0

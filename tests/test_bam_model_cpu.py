@@ -72,7 +72,7 @@ def test_quality_filter_signed_chars(min_phred, q, status):
 
 
 def test_first_occurrence_wins_and_numeric_closes():
-    # host/bam_ingest.cpp:571-610: the first string occurrence of a name is the value ...
+    # host/bam_ingest.cpp:474-513: the first string occurrence of a name is the value ...
     r = row([("CB", "Z", CB), ("CB", "Z", "AAAA"), ("UB", "Z", UMI)])
     assert r.cb == bm.pack(CB.encode())
     # ... and a numeric one first makes the name absent for the rest of the record
