@@ -4,6 +4,7 @@
 #include "k_inflate.h"
 #include "k_inflate_par.h"
 #include "k_bamparse.h"
+#include "k_bamtag.h"
 #include "util.h"
 
 #include <atomic>
@@ -279,6 +280,21 @@ struct dropest_bam_decoder {
 	std::atomic<bool> up_ready[2] = {{false}, {false}};   // written by the reader thread (dropest_bam_decoder_upload), read by the window call: release / acquire around up_len / up_blocks
 	// ... and their block table, made by the same caller (a walk from header to header is one cache miss per block: ~2 ms per 64 MB window)
 	struct UpBlocks { std::vector<uint64_t> in_off, out_off; std::vector<uint32_t> in_len, out_len, crc; uint64_t n = 0, used = 0, total = 0; bool ok = false; } up_blocks[2];
+	// -b (dropest_bam_decoder_set_tagging / _tag_window; k_bamtag.h): the output configuration, the annotation's gene names under -g, the sizes and
+	// offsets of the last window's output records and the output itself
+	bool tagging = false, tg_has_names = false;
+	BamTagCfg tg_cfg{};
+	DevBuf<uint32_t> tg_name_off, tg_size, tg_tile_written, tg_flags;
+	DevBuf<uint8_t> tg_name_pool, tg_out;
+	DevBuf<unsigned long long> tg_tile_bytes;
+	DevBuf<uint64_t> tg_off;
+	PinnedBuf<unsigned long long> h_tag;       // all bytes, records written, flags: stored by the scan kernel
+	uint32_t tg_n_names = 0;
+	uint64_t tg_len = 0;                       // bytes of the last tagged window in tg_out
+	hipEvent_t tg_ev[4] = {nullptr, nullptr, nullptr, nullptr};      // around plan + scan, around emit
+	bool tg_pending = false;                   // the last emit's flag and time have not been looked at yet (tag_collect, after a wait that is made anyway)
+	double tg_ms = 0;                          // plan + scan + emit by device events, since the decoder was created or reset
+	uint64_t tg_bytes_in = 0, tg_bytes_out = 0;
 };
 
 // The decoder's streams exist from here on (the helper thread of dropest_bam_decoder_create is joined by the first call that needs them)
@@ -370,6 +386,7 @@ extern "C" int dropest_bam_decoder_reset(dropest_bam_decoder *d, const dropest_b
 		std::memcpy(&d->cfg, cfg, sizeof(BamParseCfg));
 		d->tail_len = 0; d->last_n_rec = 0; d->last_n_ok = 0; d->next_front = 0; d->last_front = 0;
 		d->annotation = nullptr; d->n_ann_genes = 0; d->n_gene_names = 0;
+		d->tagging = false; d->tg_has_names = false; d->tg_pending = false; d->tg_len = 0; d->tg_ms = 0; d->tg_bytes_in = d->tg_bytes_out = 0;      // (the names were the annotation's)
 		d->d_chr.ensure(size_t(std::max(1, cfg->n_refs)));
 		HIP_CHECK(hipMemsetAsync(d->g_vals.p, 0, size_t(d->g_mask + 1) * 4, d->stream));
 		HIP_CHECK(hipMemsetAsync(d->d_chr.p, 0xFF, d->d_chr.n * 4, d->stream));
@@ -563,6 +580,7 @@ extern "C" void dropest_bam_decoder_destroy(dropest_bam_decoder *d) {
 	(void)hipStreamSynchronize(d->up_stream);
 	for (hipEvent_t e : d->up_done) if (e) (void)hipEventDestroy(e);
 	for (hipEvent_t e : d->piece_done) if (e) (void)hipEventDestroy(e);
+	for (hipEvent_t e : d->tg_ev) if (e) (void)hipEventDestroy(e);
 	// the inflate scratch of every stream the decoder inflated on (a lent one it still holds, its own, its fronts')
 	if (d->stream && d->stream != d->own_stream) bgzf_release_inflate_scratch(d->device, d->stream);
 	if (d->own_stream) bgzf_release_inflate_scratch(d->device, d->own_stream);
@@ -1080,4 +1098,149 @@ extern "C" int dropest_bam_decoder_patch(dropest_bam_decoder *d, const uint32_t 
 		HIP_CHECK(hipGetLastError());
 		HIP_CHECK(hipStreamSynchronize(d->stream));
 	});
+}
+
+// ---- -b: the accepted records of the LAST window with their tags edited (k_bamtag.h) --------------------------------------------------------
+extern "C" int dropest_bam_decoder_set_tagging(dropest_bam_decoder *d, const dropest_bam_tag_cfg *cfg) {
+	return bgzf_guarded([&] {
+		if (!d) throw InvalidError("null argument");
+		d->tagging = false; d->tg_has_names = false; d->tg_len = 0;
+		if (!cfg) return;
+		static_assert(sizeof(BamTagCfg) == 12 + 12 + 72, "the C struct's first members and the kernels' struct are one layout");
+		for (int k = 0; k < 3; ++k) if (cfg->type_len[k] > 24) throw InvalidError("read-type values longer than 24 characters");
+		if (!cfg->out_tag[1] || !cfg->out_tag[2]) throw InvalidError("the raw barcode and raw UMI tags need two-letter names");
+		if (cfg->n_gene_names && (!cfg->gene_name_off || !cfg->gene_name_pool)) throw InvalidError("null argument");
+		HIP_CHECK(hipSetDevice(d->device));
+		bam_ready(d);
+		HIP_CHECK(hipStreamSynchronize(d->stream));
+		for (int k = 0; k < 5; ++k) d->tg_cfg.out_tag[k] = cfg->out_tag[k];
+		d->tg_cfg.type_tag = cfg->type_tag;
+		for (int k = 0; k < 3; ++k) { d->tg_cfg.type_len[k] = cfg->type_len[k]; std::memcpy(d->tg_cfg.type_val[k], cfg->type_val[k], 24); }
+		if (cfg->n_gene_names) {
+			const uint32_t n = cfg->n_gene_names, bytes = cfg->gene_name_off[n];
+			for (uint32_t g = 0; g < n; ++g) if (cfg->gene_name_off[g] > cfg->gene_name_off[g + 1]) throw InvalidError("the gene names' offsets must not decrease");
+			d->tg_name_off.ensure(size_t(n) + 1); d->tg_name_pool.ensure(size_t(bytes) + 16);
+			d->h_dict.ensure((size_t(n) + 1) * 4 + size_t(bytes) + 128);
+			size_t at = 0;
+			bam_to_device(d, d->tg_name_off.p, cfg->gene_name_off, (size_t(n) + 1) * 4, at);
+			if (bytes) bam_to_device(d, d->tg_name_pool.p, cfg->gene_name_pool, bytes, at);
+			HIP_CHECK(hipStreamSynchronize(d->stream));
+			d->tg_n_names = n; d->tg_has_names = true;
+		}
+		d->tagging = true;
+	});
+}
+
+// After a wait on the decoder's stream: the last emit's size flag and its time by the device's events
+static void tag_collect(dropest_bam_decoder *d) {
+	if (!d->tg_pending) return;
+	d->tg_pending = false;
+	float ms = 0;
+	HIP_CHECK(hipEventElapsedTime(&ms, d->tg_ev[2], d->tg_ev[3]));
+	d->tg_ms += ms;
+	if (uint32_t(d->h_tag.p[3]) & BAMTAG_FLAG_SIZE) throw DeviceError("internal: a tagged record did not have the size that was planned for it");
+}
+
+// -g: the host's answer for records whose gene the annotation query left to it, before the window is tagged (again)
+extern "C" int dropest_bam_decoder_patch_annotation(dropest_bam_decoder *d, const uint32_t *rec, const uint32_t *ann_gene, const uint32_t *mark, uint32_t n) {
+	return bgzf_guarded([&] {
+		if (!d || (n && (!rec || !ann_gene || !mark))) throw InvalidError("null argument");
+		if (!d->annotation) throw InvalidError("no annotation was given to this decoder");
+		if (!n) return;
+		for (uint32_t k = 0; k < n; ++k) if (rec[k] >= d->last_n_rec) throw RangeError("record index outside the window");
+		HIP_CHECK(hipSetDevice(d->device));
+		bam_ready(d);
+		HIP_CHECK(hipStreamSynchronize(d->stream));
+		d->h_patch.ensure(size_t(n) * 2 + 8);      // words of 8 bytes: rec | gene | mark, 4 bytes each
+		uint32_t *const q_rec = reinterpret_cast<uint32_t *>(d->h_patch.p), *const q_gene = q_rec + n, *const q_mark = q_gene + n;
+		std::memcpy(q_rec, rec, size_t(n) * 4); std::memcpy(q_gene, ann_gene, size_t(n) * 4); std::memcpy(q_mark, mark, size_t(n) * 4);
+		hipLaunchKernelGGL(bam_tag_patch_annotation_kernel, dim3((n + 255) / 256), dim3(256), 0, d->stream, q_rec, q_gene, q_mark, n, d->a_gene.p, d->a_mark.p, d->o_aux.p);
+		HIP_CHECK(hipGetLastError());
+		HIP_CHECK(hipStreamSynchronize(d->stream));
+	});
+}
+
+extern "C" int dropest_bam_decoder_tag_window(dropest_bam_decoder *d, const uint8_t **d_out, uint64_t *len, uint64_t *n_written) {
+	bool undecided = false;
+	const int rc = bgzf_guarded([&] {
+		if (!d || !d_out || !len || !n_written) throw InvalidError("null argument");
+		*d_out = nullptr; *len = 0; *n_written = 0;
+		if (!d->tagging) throw InvalidError("tagging is not configured for this decoder (dropest_bam_decoder_set_tagging)");
+		if (d->annotation && !d->tg_has_names) throw InvalidError("with an annotation the tagging configuration must bring its gene names");
+		d->tg_len = 0;
+		const uint64_t n_rec = d->last_n_rec;
+		if (!n_rec) return;
+		HIP_CHECK(hipSetDevice(d->device));
+		bam_ready(d);
+		hipStream_t st = d->stream;
+		BamFront &F = d->front[d->last_front];
+		const uint32_t tiles = uint32_t((n_rec + BAMTAG_SCAN_TILE - 1) / BAMTAG_SCAN_TILE);
+		const size_t rc = size_t(n_rec) + size_t(n_rec) / 4;
+		d->tg_size.ensure(rc); d->tg_off.ensure(rc); d->tg_tile_bytes.ensure(tiles + tiles / 4 + 1); d->tg_tile_written.ensure(tiles + tiles / 4 + 1); d->tg_flags.ensure(1);
+		d->h_tag.ensure(4);
+		for (hipEvent_t &e : d->tg_ev) if (!e) HIP_CHECK(hipEventCreate(&e));
+		const bool ann = d->annotation != nullptr;
+		const BamTagIn in{F.data(), d->rec_off.p, d->o_status.p, d->o_aux.p, uint32_t(n_rec), ann ? d->a_gene.p : nullptr, ann ? d->a_mark.p : nullptr};
+		const BamTagNames names{ann ? d->tg_name_off.p : nullptr, d->tg_name_pool.p, d->tg_n_names};
+		const uint32_t grid = uint32_t((n_rec + BAMTAG_WAVES - 1) / BAMTAG_WAVES);
+		HIP_CHECK(hipMemsetAsync(d->tg_flags.p, 0, 4, st));
+		HIP_CHECK(hipEventRecord(d->tg_ev[0], st));
+		hipLaunchKernelGGL(bam_tag_plan_kernel, dim3(grid), dim3(BAMTAG_T), 0, st, in, d->cfg, d->tg_cfg, names, d->tg_size.p, d->tg_flags.p);
+		hipLaunchKernelGGL(bam_tag_tile_sum_kernel, dim3(tiles), dim3(256), 0, st, d->tg_size.p, uint32_t(n_rec), d->tg_tile_bytes.p, d->tg_tile_written.p);
+		hipLaunchKernelGGL(bam_tag_tile_scan_kernel, dim3(1), dim3(1024), 0, st, d->tg_tile_bytes.p, d->tg_tile_written.p, tiles, d->tg_flags.p, d->h_tag.p);
+		hipLaunchKernelGGL(bam_tag_offsets_kernel, dim3(tiles), dim3(256), 0, st, d->tg_size.p, uint32_t(n_rec), d->tg_tile_bytes.p, d->tg_off.p);
+		HIP_CHECK(hipGetLastError());
+		HIP_CHECK(hipEventRecord(d->tg_ev[1], st));
+		HIP_CHECK(hipStreamSynchronize(st));      // the one total that sizes the output: the only wait of the call
+		tag_collect(d);                           // (the window before: its emit is through as well)
+		float ms_plan = 0;
+		HIP_CHECK(hipEventElapsedTime(&ms_plan, d->tg_ev[0], d->tg_ev[1]));
+		d->tg_ms += ms_plan;
+		const uint64_t total = d->h_tag.p[0], written = d->h_tag.p[1];
+		if (d->h_tag.p[2] & BAMTAG_FLAG_UNDECIDED) {
+			undecided = true;
+			throw UnsupportedError("the annotation query left the gene of some reads to the host: give their genes and marks with dropest_bam_decoder_patch_annotation and tag the window again");
+		}
+		if (written != d->last_n_ok) throw DeviceError("internal: the tagged records and the window's counters disagree");
+		d->tg_out.ensure(size_t(total) + size_t(total) / 8 + 64);
+		HIP_CHECK(hipEventRecord(d->tg_ev[2], st));      // (the kernels' time: the host's wait and the allocation between them are not theirs)
+		hipLaunchKernelGGL(bam_tag_emit_kernel, dim3(grid), dim3(BAMTAG_T), 0, st, in, d->cfg, d->tg_cfg, names, d->tg_size.p, d->tg_off.p, d->tg_out.p, total, d->tg_flags.p);
+		HIP_CHECK(hipGetLastError());
+		hipLaunchKernelGGL(bam_words_to_host_kernel, dim3(1), dim3(256), 0, st, d->tg_flags.p, reinterpret_cast<uint32_t *>(d->h_tag.p + 3), 1u);
+		HIP_CHECK(hipGetLastError());
+		HIP_CHECK(hipEventRecord(d->tg_ev[3], st));
+		d->tg_pending = true;                     // its flag (plan and emit disagree: internal) and its time are read after the next wait on the stream
+		d->tg_bytes_in += F.data_len; d->tg_bytes_out += total;
+		d->tg_len = total;
+		*d_out = d->tg_out.p; *len = total; *n_written = written;
+	});
+	return rc && undecided ? 2 : rc;
+}
+
+extern "C" int dropest_bam_decoder_tagged_to_host(dropest_bam_decoder *d, uint8_t *dst, uint64_t cap) {
+	return bgzf_guarded([&] {
+		if (!d || (d->tg_len && !dst)) throw InvalidError("null argument");
+		if (d->tg_len > cap) throw InvalidError("destination too small: " + std::to_string(d->tg_len) + " bytes needed");
+		if (!d->tg_len) return;
+		HIP_CHECK(hipSetDevice(d->device));
+		bam_ready(d);
+		HIP_CHECK(hipMemcpyAsync(dst, d->tg_out.p, d->tg_len, hipMemcpyDeviceToHost, d->stream));
+		HIP_CHECK(hipStreamSynchronize(d->stream));
+		tag_collect(d);
+	});
+}
+
+extern "C" int dropest_bam_decoder_tag_stats(dropest_bam_decoder *d, double *kernel_ms, uint64_t *bytes_in, uint64_t *bytes_out) {
+	if (!d) return 1;
+	if (d->tg_pending && bgzf_guarded([&] { HIP_CHECK(hipSetDevice(d->device)); HIP_CHECK(hipStreamSynchronize(d->stream)); tag_collect(d); })) return 1;
+	if (kernel_ms) *kernel_ms = d->tg_ms;
+	if (bytes_in) *bytes_in = d->tg_bytes_in;
+	if (bytes_out) *bytes_out = d->tg_bytes_out;
+	return 0;
+}
+
+extern "C" void *dropest_bam_decoder_stream(dropest_bam_decoder *d) {
+	if (!d || hipSetDevice(d->device) != hipSuccess) return nullptr;
+	try { bam_ready(d); } catch (...) { return nullptr; }
+	return d->stream;
 }

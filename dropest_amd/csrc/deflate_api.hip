@@ -175,3 +175,109 @@ extern "C" int dropest_deflate_batch_run(dropest_deflate_batch *b, uint64_t len,
 }
 
 extern "C" void dropest_deflate_batch_destroy(dropest_deflate_batch *b) { delete b; }
+
+// ---- a stream of bytes that are on the device already (the tagged BAM output, -b) ---------------------------------------------------------
+struct dropest_deflate_stream {
+	int device = 0;
+	hipStream_t stream = nullptr;
+	uint64_t batch = 0, fill = 0, out_cap = 0;
+	dropest_deflate_write write = nullptr;
+	void *user = nullptr;
+	DevBuf<uint8_t> d_in, d_out, scratch;
+	DevBuf<uint32_t> d_member_len;
+	DevBuf<uint64_t> d_totals;
+	PinnedBuf<uint8_t> h_out;
+	PinnedBuf<uint64_t> h_totals;
+	hipEvent_t ev[2] = {nullptr, nullptr};
+	double kernel_ms = 0;
+	uint64_t bytes_in = 0, bytes_out = 0, n_batches = 0;
+	~dropest_deflate_stream() { (void)hipSetDevice(device); (void)hipStreamSynchronize(stream); for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+};
+
+namespace {
+// the first `len` bytes collected so far: one launch, the members to pinned memory, then to the caller
+void deflate_stream_flush(dropest_deflate_stream *s, uint64_t len, int flags) {
+	const DeflateLayout lay(len, flags);
+	if (!lay.n_members) return;
+	// The launches of dropest_bgzf_deflate_device with a scratch buffer that is the handle's own, as dropest_deflate_batch has one.  With that
+	// call's scratch from the stream-ordered pool, blocks came out damaged (sizes right, payload bits wrong, other blocks each run) whenever the
+	// BAM decoder inflated its next window on another stream meanwhile (DROPEST_BAM_PIPELINE=1; measured: 9-22 of 161 blocks, none with this
+	// buffer, none with a device-wide wait in front of the launch).
+	deflate_check(lay, s->d_in.p, len, s->d_out.p, s->d_member_len.p, s->d_member_len.n, s->d_totals.p);
+	s->scratch.ensure(lay.bytes);
+	HIP_CHECK(hipEventRecord(s->ev[0], s->stream));
+	deflate_launch(s->stream, lay, s->scratch.p, s->d_in.p, len, s->d_out.p, s->out_cap, s->d_member_len.p, s->d_totals.p);
+	HIP_CHECK(hipEventRecord(s->ev[1], s->stream));
+	HIP_CHECK(hipMemcpyAsync(s->h_totals.p, s->d_totals.p, 24, hipMemcpyDeviceToHost, s->stream));
+	HIP_CHECK(hipStreamSynchronize(s->stream));
+	const uint64_t total = s->h_totals.p[1];
+	if (s->h_totals.p[2] || total > s->out_cap || s->h_totals.p[0] != lay.n_members) throw DeviceError("the deflate kernels reported an impossible size");
+	float ms = 0;
+	HIP_CHECK(hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
+	s->kernel_ms += ms; s->bytes_in += len; s->bytes_out += total; ++s->n_batches;
+	s->h_out.ensure(total);
+	HIP_CHECK(hipMemcpyAsync(s->h_out.p, s->d_out.p, total, hipMemcpyDeviceToHost, s->stream));
+	HIP_CHECK(hipStreamSynchronize(s->stream));
+	if (s->write(s->h_out.p, total, s->user)) throw IoError("the compressed bytes could not be written");
+}
+}  // namespace
+
+extern "C" int dropest_deflate_stream_create(int device, void *stream, uint64_t batch_bytes, dropest_deflate_write write, void *user, dropest_deflate_stream **out) {
+	return deflate_guarded([&] {
+		if (!out || !write) throw InvalidError("null argument");
+		*out = nullptr;
+		int n_dev = 0;
+		if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev) throw DeviceError("no such GPU: BGZF blocks are deflated on the device only here");
+		HIP_CHECK(hipSetDevice(device));
+		std::unique_ptr<dropest_deflate_stream> s(new dropest_deflate_stream());
+		// whole chunks, so that every block but a file's last is full; at most 64 MB, so that a launch's scratch (about 5 x its input) stays bounded
+		const uint64_t chunks = std::max<uint64_t>(1, std::min<uint64_t>(batch_bytes ? batch_bytes : ~0ull, uint64_t(64) << 20) / DFL_CHUNK);
+		s->device = device; s->stream = hipStream_t(stream); s->batch = chunks * DFL_CHUNK; s->write = write; s->user = user;
+		s->out_cap = dropest_bgzf_deflate_bound(s->batch);
+		s->d_in.alloc(s->batch); s->d_out.alloc(s->out_cap); s->d_member_len.alloc(chunks + 1); s->d_totals.alloc(3);
+		s->h_totals.ensure_exact(3, hipHostMallocDefault);
+		for (hipEvent_t &e : s->ev) HIP_CHECK(hipEventCreate(&e));
+		*out = s.release();
+	});
+}
+
+extern "C" int dropest_deflate_stream_put(dropest_deflate_stream *s, const uint8_t *src, uint64_t len, int on_device) {
+	return deflate_guarded([&] {
+		if (!s || (len && !src)) throw InvalidError("null argument");
+		HIP_CHECK(hipSetDevice(s->device));
+		while (len) {
+			const uint64_t take = std::min(len, s->batch - s->fill);
+			HIP_CHECK(hipMemcpyAsync(s->d_in.p + s->fill, src, take, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s->stream));
+			if (!on_device) HIP_CHECK(hipStreamSynchronize(s->stream));      // (the caller's host bytes are its own again)
+			s->fill += take; src += take; len -= take;
+			if (s->fill == s->batch) { s->fill = 0; deflate_stream_flush(s, s->batch, 0); }
+		}
+	});
+}
+
+extern "C" int dropest_deflate_stream_finish(dropest_deflate_stream *s, int flags) {
+	return deflate_guarded([&] {
+		if (!s) throw InvalidError("null argument");
+		HIP_CHECK(hipSetDevice(s->device));
+		const uint64_t rest = s->fill;
+		s->fill = 0;
+		if (rest) deflate_stream_flush(s, rest, flags);
+		else if (flags & DROPEST_DEFLATE_EOF) {      // nothing is left over: the end-of-file block alone (SAMv1 section 4.1.2)
+			static const uint8_t eof[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+			HIP_CHECK(hipStreamSynchronize(s->stream));
+			if (s->write(eof, sizeof(eof), s->user)) throw IoError("the compressed bytes could not be written");
+			s->bytes_out += sizeof(eof);
+		}
+	});
+}
+
+extern "C" int dropest_deflate_stream_stats(const dropest_deflate_stream *s, double *kernel_ms, uint64_t *bytes_in, uint64_t *bytes_out, uint64_t *n_batches) {
+	if (!s) return 1;
+	if (kernel_ms) *kernel_ms = s->kernel_ms;
+	if (bytes_in) *bytes_in = s->bytes_in;
+	if (bytes_out) *bytes_out = s->bytes_out;
+	if (n_batches) *n_batches = s->n_batches;
+	return 0;
+}
+
+extern "C" void dropest_deflate_stream_destroy(dropest_deflate_stream *s) { delete s; }

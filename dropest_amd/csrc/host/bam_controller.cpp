@@ -233,18 +233,32 @@ void BamController::read_file_on_host(FileIngest &file, bool first_file) {
 	file.sw.trace("[bam] bulk windows: parse + pack on the workers %.1f ms, new dictionary entries %.1f ms, container %.1f ms\n", file.bulk.ms[0], file.bulk.ms[1], file.bulk.ms[2]);
 }
 
-void BamController::parse_bam_files(const std::vector<std::string> &bam_files, CellsDataContainer &container) {
+void BamController::parse_bam_files(const std::vector<std::string> &bam_files, CellsDataContainer &container) { parse_bam_files(bam_files, false, container); }
+
+void BamController::parse_bam_files(const std::vector<std::string> &bam_files, bool print_result_bams, CellsDataContainer &container) {
 	const BamSwitches sw = BamSwitches::from_environment();
+	_tagged.clear();
+	if (print_result_bams) {      // what the device path refuses, said before any file is read: the host reader does not write BAM
+		const char *why = nullptr;
+		if (_params_from_files) why = "read-parameter files (-r) are served by the host reader";
+		else if (_gene_in_chromosome_name) why = "gene = chromosome name is resolved by the host reader";
+		else if (_tags.intronic_read_value.size() > 24 || _tags.intergenic_read_value.size() > 24 || _tags.exonic_read_value.size() > 24) why = "a read-type value is longer than 24 bytes";
+		if (why) throw std::runtime_error(std::string("Tagged BAM output (-b) is written on the device BAM path only, which this configuration cannot take: ") + why);
+		_tagged.reserve(bam_files.size());
+	}
 	const unsigned nthreads = _threads ? _threads : std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
 	struct SayAll { const BamSwitches &sw; clk::time_point t; ~SayAll() { sw.trace("[bam] parse_bam_files: %.1f ms\n", since(t)); } } say_all{sw, clk::now()};
 	join_release_thread();
 	for (auto const &bam_name : bam_files) {
 		FileIngest file(sw, bam_name, bam_files.size(), container, _counters, _tags, _filled_bam, _params_from_files, _gene_in_chromosome_name, _min_barcode_phred, _genes, nthreads);
-		if (_device_decode || sw.device) {
+		if (print_result_bams) { _tagged.emplace_back(); file.tagged = &_tagged.back(); }
+		if (print_result_bams || _device_decode || sw.device) {
 			const auto t_df = clk::now();
 			const bool done = read_file_on_device(file);
 			sw.trace("[bam] device path: %.1f ms in all for this file (taken: %d)\n", since(t_df), int(done));
 			if (done) continue;
+			if (print_result_bams)
+				throw std::runtime_error("Tagged BAM output (-b) is written on the device BAM path only, which cannot take this file: " + (file.refusal.empty() ? std::string("unknown reason") : file.refusal) + ": " + bam_name);
 		}
 		read_file_on_host(file, &bam_name == &bam_files.front());
 	}

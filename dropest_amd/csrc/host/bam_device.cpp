@@ -7,12 +7,16 @@
 // exactly like the Needs of BulkWindow.  Windows grow from 1 MB of compressed bytes (the first ones meet most gene names).
 // Every block's CRC-32 is checked on the device (the wave that inflated it reads it back).  Falls back to the host reader (returns false before anything was added) when
 // the configuration needs what the kernels do not do: -r parameter files, gene = chromosome name.
+// Tagged BAM output (-b: parse_bam_files(files, true, container)) is made here and only here: every window's accepted records are edited on the device
+// (csrc/k_bamtag.h) before the window goes into the container, compressed there and written to `<input stem>.tagged.bam` (open_tagged, tag_window,
+// close_tagged); a file this path refuses is then an error that names the reason (FileIngest::refusal), not a file for the host reader.
 // A sharded container is fed the same way: ONE decoder, on the GPU of the shard the file's first read goes to and on that shard's stream, for the
 // whole file (the record cut off at a window's end waits inside it); the container cuts every window at its quota boundaries and appends the
 // pieces to the shards' resident reads, device to device.
 #include "bam_parse.h"
 #include "../../../include/dropest_bgzf.h"
 #include "../../../include/dropest_annotation.h"
+#include "../../../include/dropest_deflate.h"
 
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -167,6 +171,21 @@ class DeviceFileReader {
 	std::atomic<size_t> stretched_windows{0};
 	std::future<Staged> next;
 	struct Drain { std::future<Staged> &f; ~Drain() { if (f.valid()) f.wait(); } };   // (an exception must not leave the reader running on freed buffers)
+	// -b (bam_ingest.h: parse_bam_files(files, true, container)): the decoder writes every window's accepted records again with their tags edited
+	// (dropest_bam_decoder_tag_window), a compressor stream on the decoder's stream collects them and hands BGZF blocks to the file in order.
+	// Declared behind the decoder: it goes first, while the stream it was lent is still the decoder's.
+	struct TaggedOut {
+		std::FILE *f = nullptr;
+		dropest_deflate_stream *z = nullptr;
+		~TaggedOut() { if (z) dropest_deflate_stream_destroy(z); if (f) std::fclose(f); }
+		static int write(const uint8_t *bytes, uint64_t len, void *user) { return std::fwrite(bytes, 1, size_t(len), static_cast<TaggedOut *>(user)->f) == size_t(len) ? 0 : 1; }
+	} tagged;
+	std::vector<uint8_t> header_bytes;      // magic, text, references: the tagged file begins with them, byte for byte
+	void open_tagged();
+	void tag_window(const dropest_bam_window &w);
+	void patch_host_decided(const dropest_bam_window &w);
+	std::unordered_map<std::string, uint32_t> ann_gene_index;      // -g: the annotation's gene names -> its gene indices
+	void close_tagged();
 
 	[[noreturn]] void fail() const { throw std::runtime_error(std::string(dropest_bgzf_last_error()) + ": " + file.bam_name); }
 
@@ -248,7 +267,8 @@ void DeviceFileReader::read_header() {
 		h += 4 + ln + 4;
 	}
 	container.set_reference_names(refs);
-	c0 = at; u0 = 0;                                 // the header ends with a block: the records open the next one
+	if (file.tagged) header_bytes.assign(hdr.begin(), hdr.begin() + h);
+	c0 = at; u0 = 0;                                // the header ends with a block: the records open the next one
 	for (size_t k = starts.size(); k-- > 0;)
 		if (starts[k].second <= h && h < (k + 1 < starts.size() ? starts[k + 1].second : hdr.size())) { c0 = starts[k].first; u0 = uint32_t(h - starts[k].second); break; }
 }
@@ -301,6 +321,82 @@ bool DeviceFileReader::annotation_to_device() {
 	for (size_t g = 0; g < flat.gene_names.size(); ++g) ann_gene_hash[g] = CellsDataContainer::hash_name(flat.gene_names[g]);
 	id_of_ann_gene.assign(flat.gene_names.size(), -1);
 	return true;
+}
+
+// (c) -b: the output tag names and read-type values (BamTags.cpp:7-24; an out-value is the configured in-value, else EXONIC / INTRONIC /
+// INTERGENIC), under -g the annotation's gene names; `<input stem>.tagged.bam` in the current directory (BamProcessor::get_result_bam_name,
+// BamProcessorAbstract::update_bam strips the directory); the header's bytes go in first
+void DeviceFileReader::open_tagged() {
+	const BamTags &t = parser.tags;
+	dropest_bam_tag_cfg tc{};
+	const std::string *names[5] = {&t.gene, &t.cell_barcode_raw, &t.umi_raw, &t.cell_barcode_quality, &t.umi_quality};
+	for (int k = 0; k < 5; ++k) tc.out_tag[k] = RecordParser::tag16(*names[k]);
+	tc.type_tag = RecordParser::tag16(t.read_type);
+	const std::string values[3] = {t.exonic_read_value.empty() ? "EXONIC" : t.exonic_read_value, t.intronic_read_value.empty() ? "INTRONIC" : t.intronic_read_value,
+	                               t.intergenic_read_value.empty() ? "INTERGENIC" : t.intergenic_read_value};
+	for (int k = 0; k < 3; ++k) { tc.type_len[k] = uint32_t(values[k].size()); std::memcpy(tc.type_val[k], values[k].data(), std::min<size_t>(values[k].size(), 24)); }
+	std::vector<uint32_t> off; std::vector<uint8_t> pool;
+	if (ann.a) {
+		off.push_back(0);
+		for (const std::string &g : flat.gene_names) { pool.insert(pool.end(), g.begin(), g.end()); off.push_back(uint32_t(pool.size())); ann_gene_index.emplace(g, uint32_t(ann_gene_index.size())); }
+		pool.push_back(0);
+		tc.gene_name_off = off.data(); tc.gene_name_pool = pool.data(); tc.n_gene_names = uint32_t(flat.gene_names.size());
+	}
+	if (dropest_bam_decoder_set_tagging(dec, &tc)) fail();
+	std::string name = file.bam_name.substr(0, file.bam_name.find_last_of('.')) + ".tagged.bam";
+	const size_t slash = name.find_last_of("\\/");
+	if (slash != std::string::npos) name = name.substr(slash + 1);
+	file.tagged->name = name;
+	tagged.f = std::fopen(name.c_str(), "wb");
+	if (!tagged.f) throw std::runtime_error("Can't write tagged BAM file: " + name);
+	if (dropest_deflate_stream_create(target.device, dropest_bam_decoder_stream(dec), sw.tagged_batch, TaggedOut::write, &tagged, &tagged.z) ||
+	    dropest_deflate_stream_put(tagged.z, header_bytes.data(), header_bytes.size(), 0))
+		throw std::runtime_error(std::string(dropest_deflate_last_error()) + ": " + name);
+}
+
+// (g) -b: the window the decoder holds, tagged, to the compressor (on the decoder's stream: the bytes are copied before the next window overwrites them)
+void DeviceFileReader::tag_window(const dropest_bam_window &w) {
+	const uint8_t *d_out = nullptr;
+	uint64_t len = 0, written = 0;
+	int rc = dropest_bam_decoder_tag_window(dec, &d_out, &len, &written);
+	if (rc == 2) { patch_host_decided(w); rc = dropest_bam_decoder_tag_window(dec, &d_out, &len, &written); }
+	if (rc) fail();
+	if (len && dropest_deflate_stream_put(tagged.z, d_out, len, 1)) throw std::runtime_error(std::string(dropest_deflate_last_error()) + ": " + file.tagged->name);
+	++file.tagged->windows; file.tagged->records += size_t(written);
+}
+
+// (g) -b with -g: reads at loci with more transcripts at an end point than the annotation kernel holds come back among the window's need records with
+// no verdict; the host's annotation decides them (as resolve_new does for the container), and the tag kernels are given its gene and mark
+void DeviceFileReader::patch_host_decided(const dropest_bam_window &w) {
+	const size_t m = w.n_need;
+	size_t bytes = 0;
+	for (size_t k = 0; k < m; ++k) bytes += w.need_size[k];
+	need_bytes.resize(bytes + 16); need_off.resize(m);
+	if (dropest_bam_decoder_fetch_records(dec, w.need_rec, uint32_t(m), need_bytes.data(), need_bytes.size(), need_off.data())) fail();
+	std::vector<uint32_t> rec, gene, mark;
+	Parsed tmp;
+	for (size_t k = 0; k < m; ++k) {
+		parser.parse(need_bytes.data() + need_off[k], tmp);
+		if (tmp.status != Parsed::OK) throw std::runtime_error("internal: the device and the host read a BAM record differently: " + file.bam_name);
+		const auto it = tmp.r.gene.empty() ? ann_gene_index.end() : ann_gene_index.find(std::string(tmp.r.gene));
+		rec.push_back(w.need_rec[k]); gene.push_back(it == ann_gene_index.end() ? 0xFFFFFFFFu : it->second); mark.push_back(tmp.r.mark);
+	}
+	if (dropest_bam_decoder_patch_annotation(dec, rec.data(), gene.data(), mark.data(), uint32_t(m))) fail();
+}
+
+// (h) -b: what is left over, the end-of-file block, and the account of what was written
+void DeviceFileReader::close_tagged() {
+	BamController::TaggedFile &t = *file.tagged;
+	if (dropest_deflate_stream_finish(tagged.z, DROPEST_DEFLATE_EOF)) throw std::runtime_error(std::string(dropest_deflate_last_error()) + ": " + t.name);
+	uint64_t in = 0, out = 0, batches = 0, tag_in = 0, tag_out = 0;
+	(void)dropest_deflate_stream_stats(tagged.z, &t.deflate_ms, &in, &out, &batches);
+	(void)dropest_bam_decoder_tag_stats(dec, &t.tag_ms, &tag_in, &tag_out);
+	t.inflated_bytes = size_t(in); t.compressed_bytes = size_t(out); t.batches = size_t(batches); t.tag_bytes_in = size_t(tag_in); t.tag_bytes_out = size_t(tag_out);
+	dropest_deflate_stream_destroy(tagged.z); tagged.z = nullptr;
+	const bool ok = std::fclose(tagged.f) == 0;
+	tagged.f = nullptr;
+	if (!ok) throw std::runtime_error("Can't write tagged BAM file: " + t.name);
+	(void)dropest_bam_decoder_set_tagging(dec, nullptr);      // (the decoder may be kept for a call that writes none)
 }
 
 // The compressed bytes reach the device in pieces: helper threads (up to eight for a long window) read the next window from the file into
@@ -497,6 +593,7 @@ void DeviceFileReader::resolve_new(const dropest_bam_window &w) {
 // (g) one decoded window into the container and the counters
 void DeviceFileReader::take_window(const dropest_bam_window &w, size_t used, clk::time_point t_call) {
 	ms_window_calls += since(t_call);
+	if (file.tagged) tag_window(w);      // first thing: whichever way the window then goes into the container, its accepted records are written
 	if (first) {
 		est_reads = size_t(double(w.n_records) * double(map.n - c0) / double(std::max<size_t>(used, 1)) * double(file.n_files) * 1.05);
 		const auto t_e = clk::now();
@@ -515,7 +612,7 @@ void DeviceFileReader::take_window(const dropest_bam_window &w, size_t used, clk
 	const bool has_q = w.any_gene && w.quality_len_max > 0;
 	const uint32_t q_len = w.quality_len_max;
 	const bool q_bulk = has_q && w.quality_len_min == w.quality_len_max && container.bulk_ingest_possible_with_quality(q_len, true);
-	if (has_q ? !q_bulk : !container.bulk_ingest_possible(true)) {
+	if ((has_q ? !q_bulk : !container.bulk_ingest_possible(true)) || (file.tagged && !container.bulk_ingest_possible_at_all(true))) {
 		records_through_host(w, n);
 		host_ms[1] += since(t_phase);
 		return;
@@ -588,12 +685,13 @@ void DeviceFileReader::windows_pipelined() {
 }
 
 bool DeviceFileReader::read() {
-	if (!open_file()) return false;
+	if (!open_file()) { file.refusal = "the file cannot be opened or mapped"; return false; }
 	read_header();
 	ms_header = since(t_enter);
-	if (!lease_decoder()) return false;
+	if (!lease_decoder()) { file.refusal = std::string("no GPU decoder (") + dropest_bgzf_last_error() + ")"; return false; }
 	ms_create = since(t_enter) - ms_header;
-	if (!annotation_to_device()) return false;
+	if (!annotation_to_device()) { file.refusal = "the gene annotation cannot be held on the device"; return false; }
+	if (file.tagged) open_tagged();
 	t_file = clk::now();
 	// (1 MB first: the file's genes and chromosomes are mostly met there, and every one of them is a record the host parses -- a first window of
 	// 4 / 8 / 16 MB: 65 -> 76 / 79 / 87 ms on the 3.2 x file; then x 8: 1, 8, 64 MB ... measured against x 4 and x 16 with the round's final decoder:
@@ -605,6 +703,7 @@ bool DeviceFileReader::read() {
 	file_at = c0;
 	read_next();
 	if (sw.pipeline) windows_pipelined(); else windows_one_by_one();
+	if (file.tagged) close_tagged();
 	sw.trace("[bam] device path: %zu windows, %.1f ms behind the header; copy in %.1f ms, inflate %.1f ms (%zu blocks left to the host), record chain %.1f ms (%zu guesses "
 	         "repaired), fields + dense columns %.1f ms; host: dictionaries to the device %.1f ms, %zu records with something new %.1f ms, container %.1f ms\n",
 	         n_windows, since(t_file), dev_ms[0], dev_ms[1], refused, dev_ms[2], repaired, dev_ms[3], host_ms[0], n_needs, host_ms[1], host_ms[2]);
@@ -619,10 +718,13 @@ bool DeviceFileReader::read() {
 
 bool read_file_on_device(FileIngest &file) {
 	const RecordParser &parser = file.parser;
-	if (parser.params_from_files || parser.gene_in_chromosome_name || !file.container.bulk_ingest_possible_at_all(true)) return false;
+	if (parser.params_from_files) { file.refusal = "read-parameter files (-r) are served by the host reader"; return false; }
+	if (parser.gene_in_chromosome_name) { file.refusal = "gene = chromosome name is resolved by the host reader"; return false; }
+	// (-b stays here whatever the container takes: a window it cannot take in bulk goes through records_through_host, record by record if need be)
+	if (!file.tagged && !file.container.bulk_ingest_possible_at_all(true)) { file.refusal = "the container no longer takes reads in bulk"; return false; }
 	const CellsDataContainer::IngestTarget target = file.container.next_read_target();
 	const auto t_enter = clk::now();
-	if (parser.tags.intronic_read_value.size() > 24 || parser.tags.intergenic_read_value.size() > 24) return false;
+	if (parser.tags.intronic_read_value.size() > 24 || parser.tags.intergenic_read_value.size() > 24) { file.refusal = "a read-type value is longer than 24 bytes"; return false; }
 	DeviceFileReader reader(file, target, t_enter);
 	return reader.read();
 }

@@ -9,7 +9,7 @@
 //   ReadParamsParser::get_gene_from_reference (-g: gene annotation from a GTF / BED file, gene_annotation.h)
 //   ReadMapParamsParser::get_read_params (-r: droptag's read-parameter files "name cb umi cb_quality umi_quality", gzip;
 //     ReadMapParamsParser.cpp:22-48, :50-108; every name serves once)
-// Not built: filtered BAM output (-F, -b).
+// Tagged BAM output (-b) is written on the device path only (parse_bam_files(files, true, container)).  Not built: filtered BAM output (-F).
 //
 // The container format: BGZF (gzip members with a 'BC' extra field, SAMv1 §4.1) holding the BAM stream (§4.2).
 // Blocks are inflated by a pool of host threads, records are parsed in stream order by the caller's thread (the
@@ -81,6 +81,13 @@ public:
 		size_t total_reads = 0, cant_parse = 0, low_quality = 0, saved = 0;
 		double wait_ms = 0, parse_ms = 0, add_ms = 0;   // waiting for decompressed data / parallel record parsing / add_record (serial)
 	};
+	// -b: one `<input stem>.tagged.bam` that parse_bam_files(files, true, container) wrote
+	struct TaggedFile {
+		std::string name;
+		size_t windows = 0, records = 0, inflated_bytes = 0, compressed_bytes = 0, batches = 0;
+		double tag_ms = 0, deflate_ms = 0;              // the tag kernels (plan, scan, emit) and the compressor's launches, by device events
+		size_t tag_bytes_in = 0, tag_bytes_out = 0;     // inflated bytes of the windows the tag kernels looked at, bytes they wrote
+	};
 private:
 	BamTags _tags;
 	struct ReadParams { std::string cb, umi, umi_quality; bool pass_quality; };
@@ -95,6 +102,7 @@ private:
 	unsigned _threads;
 	bool _device_decode = false;
 	Counters _counters;
+	std::vector<TaggedFile> _tagged;
 	Tools::GeneAnnotation::RefGenesContainer _genes;   // -g: empty unless a GTF / BED file was given
 public:
 	// gtf_path: GTF / BED annotation (-g), "" = genes come from the BAM's gene tag; read_param_filenames must be empty (not built)
@@ -102,6 +110,14 @@ public:
 	              bool gene_in_chromosome_name, int min_barcode_phred, unsigned threads = 0);
 	// BamController::parse_bam_files with a BamProcessor: every accepted read reaches container.add_record in file order
 	void parse_bam_files(const std::vector<std::string> &bam_files, CellsDataContainer &container);
+	// The reference's signature.  print_result_bams (-b): every accepted alignment of every file is also written, in file order, to
+	// `<input stem>.tagged.bam` in the current directory (BamProcessor::get_result_bam_name, BamProcessorAbstract::update_bam), with its gene, raw
+	// barcode ("CR"), raw UMI ("UR"), quality strings and read type as Z tags (BamProcessorAbstract::save_alignment; DESIGN.md section 7 has the
+	// rule).  The records are edited on the device (csrc/k_bamtag.h) and compressed there (include/dropest_deflate.h), so the device reader is used
+	// whether or not DROPEST_BAM_DEVICE is set, and what it refuses -- -r parameter files, gene = chromosome name, a read-type value over 24
+	// bytes, no GPU -- throws std::runtime_error naming the reason: the host reader does not write BAM.  false: the call above.
+	void parse_bam_files(const std::vector<std::string> &bam_files, bool print_result_bams, CellsDataContainer &container);
+	const std::vector<TaggedFile> &tagged_files() const { return _tagged; }   // of the last parse_bam_files call
 	// BGZF inflate, record chain and tag walk on the container's GPU (include/dropest_bgzf.h) where the configuration allows it: tags or read
 	// names as the source of barcode / UMI, the gene tag or a -g annotation (annotation_api.hip) as the source of the gene; not with -r or gene =
 	// chromosome name (the host reader then runs).  A sharded container is fed by one decoder on the GPU of the shard the file's first read goes to.

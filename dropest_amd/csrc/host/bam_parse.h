@@ -45,6 +45,7 @@ struct BamSwitches {
 	size_t piece_bytes = size_t(2) << 20;
 	uint32_t readers = 8;
 	size_t stretch_bytes = size_t(8) << 20, stretch_blocks = 8192;   // tests: DROPEST_BAM_TEST_STRETCH="bytes,blocks" lowers the two thresholds so that small files take the four stretches
+	size_t tagged_batch = size_t(64) << 20;                          // -b: inflated bytes per launch of the device compressor; DROPEST_BAM_TAGGED_BATCH_KB lowers it (tests: several batches from a small file)
 
 	static BamSwitches from_environment() {
 		BamSwitches s;
@@ -64,6 +65,7 @@ struct BamSwitches {
 		const bool pipeline = set("DROPEST_BAM_PIPELINE"), no_pipeline = set("DROPEST_BAM_NO_PIPELINE");
 		s.pipeline = s.upload_ahead && pipeline && !no_pipeline;
 		s.one_walker = set("DROPEST_BAM_ONE_WALKER");
+		if (const char *e = getenv("DROPEST_BAM_TAGGED_BATCH_KB")) s.tagged_batch = std::min(s.tagged_batch, size_t(std::max(64, atoi(e))) << 10);
 		if (const char *e = getenv("DROPEST_BAM_TEST_STRETCH")) { long x = 0, y = 0; if (std::sscanf(e, "%ld,%ld", &x, &y) == 2 && x > 0 && y > 0) { s.stretch_bytes = size_t(x); s.stretch_blocks = size_t(y); } }
 		return s;
 	}
@@ -296,6 +298,8 @@ struct FileIngest {
 	std::vector<std::string> refs;       // the file's reference names, from whichever reader read its header
 	RecordParser parser;
 	BulkWindow bulk;
+	BamController::TaggedFile *tagged = nullptr;   // -b: this file's tagged BAM is to be written (device path only); what was written is noted here
+	std::string refusal;                 // why the device path handed the file back (read_file_on_device returned false)
 	FileIngest(const BamSwitches &sw, const std::string &bam_name, size_t n_files, CellsDataContainer &container, BamController::Counters &counters,
 	           const BamTags &tags, bool filled_bam, bool params_from_files, bool gene_in_chromosome_name, int min_barcode_phred,
 	           const Tools::GeneAnnotation::RefGenesContainer &genes, unsigned threads)

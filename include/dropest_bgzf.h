@@ -157,6 +157,43 @@ int dropest_bam_decoder_quality_rows(dropest_bam_decoder *d, uint32_t ql, const 
 int dropest_bam_decoder_patch(dropest_bam_decoder *d, const uint32_t *pos, const uint64_t *cb, const uint64_t *umi, const uint32_t *gene,
                               const uint32_t *aux, uint32_t n);
 
+/* ---- -b: tagged BAM output (csrc/k_bamtag.h; DESIGN.md section 7 has the edit rule) ---------------------------------------------------
+ * What BamProcessorAbstract::save_alignment (BamProcessorAbstract.cpp:65-114) writes for every accepted alignment: the record with its gene, raw
+ * barcode, raw UMI, the two quality strings and the read type as Z tags.  Every aux entry the tag walk reaches whose name is one of the edited
+ * names is left out (every occurrence, whatever its type); the edited tags are appended in the order gene, raw barcode, raw UMI, barcode quality,
+ * UMI quality, read type; everything else in the record is a byte copy.  The gene tag is edited when the record has a gene, a quality tag when
+ * the string is not empty (-f only), the read type when a tag is configured and the mark is exactly exonic (2), intronic (4) or intergenic (1). */
+typedef struct dropest_bam_tag_cfg {
+	uint16_t out_tag[5];                 /* gene, raw barcode, raw UMI, barcode quality, UMI quality: letters lo | hi << 8 (0 = never written; not the raw two) */
+	uint16_t type_tag;                   /* read type, 0 = none */
+	uint32_t type_len[3];                /* out-values for an exonic, intronic, intergenic read: at most 24 bytes each */
+	uint8_t type_val[3][24];
+	/* -g (a decoder with an annotation): the annotation's gene names by ITS gene index, name g = pool[off[g] .. off[g + 1]); HOST memory, copied */
+	const uint32_t *gene_name_off;
+	const uint8_t *gene_name_pool;
+	uint32_t n_gene_names;
+} dropest_bam_tag_cfg;
+/* NULL turns tagging off; so does dropest_bam_decoder_reset (the names are the annotation's, which a reset drops). */
+int dropest_bam_decoder_set_tagging(dropest_bam_decoder *d, const dropest_bam_tag_cfg *cfg);
+/* Tags the LAST window (after .._window, or after .._window_finish in either window order; before the next window call): *d_out = the output
+ * records of its accepted records one after the other in file order, in a DEVICE buffer of the decoder that stays valid until the next window is
+ * tagged; *len its bytes, *n_written its records (= counts[DROPEST_BAM_OK]).  The kernels run on the decoder's stream; the call waits once, for
+ * the total that sizes the output, and returns with the emit kernel queued: work queued on that stream afterwards (dropest_bam_decoder_stream)
+ * sees the bytes, .._tagged_to_host waits for them.  Returns 0; 1 with the error set (tagging is off, ...); 2 when, under -g, the annotation
+ * query left the gene of some accepted reads to the host (more transcripts at an end point than it holds: exactly the records of the window's
+ * need list may be such): nothing was written, the caller gives the host's answer for them with .._patch_annotation and calls again. */
+int dropest_bam_decoder_tag_window(dropest_bam_decoder *d, const uint8_t **d_out, uint64_t *len, uint64_t *n_written);
+/* -g: for records rec[0 .. n) of the LAST window, the annotation's gene (its index in the annotation, 0xFFFFFFFF = none) and the UMI::Mark bits
+ * as the host decided them; read by the tag kernels only (the dense columns take the host's answer through .._patch). */
+int dropest_bam_decoder_patch_annotation(dropest_bam_decoder *d, const uint32_t *rec, const uint32_t *ann_gene, const uint32_t *mark, uint32_t n);
+/* the bytes of the last tagged window to host memory (callers and tests that want them there) */
+int dropest_bam_decoder_tagged_to_host(dropest_bam_decoder *d, uint8_t *dst, uint64_t cap);
+/* Since the decoder was created or reset: the time of the tag kernels (plan, scan, emit) by device events, the inflated bytes of the windows
+ * they looked at and the bytes they wrote (waits for the last emit).  Any pointer may be NULL. */
+int dropest_bam_decoder_tag_stats(dropest_bam_decoder *d, double *kernel_ms, uint64_t *bytes_in, uint64_t *bytes_out);
+/* The hipStream_t the decoder's kernels run on (lent or its own): work a caller queues there follows the tagged bytes in order. */
+void *dropest_bam_decoder_stream(dropest_bam_decoder *d);
+
 const char *dropest_bgzf_last_error(void);
 
 #ifdef __cplusplus

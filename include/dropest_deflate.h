@@ -29,6 +29,10 @@ uint64_t dropest_bgzf_deflate_members(uint64_t len, int flags);
  * (member_cap entries: fewer than dropest_bgzf_deflate_members(len, flags) is refused at once), d_totals[0] the number of members, d_totals[1]
  * the bytes of the whole stream, d_totals[2] = 1 when that is more than out_cap: the members that do not fit whole are then NOT written and
  * nothing is written at or beyond d_out + out_cap.  Returns 0, or 1 with dropest_deflate_last_error() set. */
+/* WARNING: not beside work on other streams.  With kernels of the same process running on other streams at the same time (the BAM decoder's
+ * pipelined windows) and other threads allocating, this call's pool scratch gave blocks of the right size with wrong payload bits (9-22 of 161,
+ * different ones every run); the cause was not found.  dropest_deflate_stream_* below makes the same launches with a buffer of its own and
+ * did not show it. */
 int dropest_bgzf_deflate_device(int device, void *stream, const uint8_t *d_in, uint64_t len, uint8_t *d_out, uint64_t out_cap,
                                 uint32_t *d_member_len, uint64_t member_cap, uint64_t *d_totals /* [3] */, int flags);
 
@@ -49,6 +53,23 @@ int dropest_deflate_batch_create(int device, uint64_t max_bytes, dropest_deflate
 int dropest_deflate_batch_input(dropest_deflate_batch *b, uint8_t **pinned);
 int dropest_deflate_batch_run(dropest_deflate_batch *b, uint64_t len, const uint8_t **out, uint64_t *out_len, uint64_t *n_members);
 void dropest_deflate_batch_destroy(dropest_deflate_batch *b);
+
+/* ---- a stream of bytes that are on the device already, to BGZF on the host (the tagged BAM output, -b) ------------------------------------
+ * The handle collects what _put gives it in a device buffer of one batch (batch_bytes cut down to whole chunks of 65 280 bytes, at most 64 MB:
+ * the scratch of a launch is about 5 x its input, and is the handle's own: dropest_deflate_stream_create's comment in csrc/deflate_api.hip says
+ * why it is not the pool's); every full batch is deflated by the launches of dropest_bgzf_deflate_device on `stream` (a hipStream_t of
+ * `device` that the caller lends; the copies run there too, so device bytes written on that stream need no other ordering), copied to pinned
+ * memory and handed to `write` in order (0 = written).  _put: `src` is DEVICE memory (on_device != 0: copied asynchronously, it must stay as it
+ * is until work queued later on the stream runs) or host memory.  _finish deflates what is left over, with `flags` (DROPEST_DEFLATE_EOF: the
+ * end-of-file block follows).  Every block but the last of a stream is a full chunk.  _stats: the deflate launches by device events, the bytes
+ * deflated and written, the batches so far.  One thread at a time. */
+typedef struct dropest_deflate_stream dropest_deflate_stream;
+typedef int (*dropest_deflate_write)(const uint8_t *bytes, uint64_t len, void *user);
+int dropest_deflate_stream_create(int device, void *stream, uint64_t batch_bytes, dropest_deflate_write write, void *user, dropest_deflate_stream **out);
+int dropest_deflate_stream_put(dropest_deflate_stream *s, const uint8_t *src, uint64_t len, int on_device);
+int dropest_deflate_stream_finish(dropest_deflate_stream *s, int flags);
+int dropest_deflate_stream_stats(const dropest_deflate_stream *s, double *kernel_ms, uint64_t *bytes_in, uint64_t *bytes_out, uint64_t *n_batches);
+void dropest_deflate_stream_destroy(dropest_deflate_stream *s);
 
 const char *dropest_deflate_last_error(void);
 
