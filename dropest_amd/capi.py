@@ -132,6 +132,11 @@ def lib():
         "dropest_simple_merge_pairs": (C.c_int, [vp, u64p, vp, vp, vp, vp]),
         "dropest_exclude_cell": (C.c_int, [vp, C.c_uint64]), "dropest_merge_cells": (C.c_int, [vp, C.c_uint64, C.c_uint64]),
         "dropest_merge_umis": (C.c_int, [vp, C.c_uint64, C.c_uint32, C.c_uint64, vp, vp]),
+        "dropest_set_save_umi_merge_targets": (C.c_int, [vp, C.c_int]),
+        "dropest_umi_merge_targets": (C.c_int, [vp, u64p, vp, vp, vp, vp]),
+        "dropest_read_corrections": (C.c_int, [vp, u64p, P(vp), P(vp), P(vp)]),
+        "dropest_read_corrections_host": (C.c_int, [vp, C.c_uint64, C.c_uint64, vp, vp, vp]),
+        "dropest_read_correction_counts": (C.c_int, [vp, vp]),
         "dropest_add_umi_to_cell": (C.c_int, [vp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, vp, C.c_uint32]),
         "dropest_umi_first_seen": (C.c_int, [vp, u64p, vp]),
         "dropest_set_umi_qualities": (C.c_int, [vp, vp, C.c_uint32, C.c_uint64]),
@@ -268,6 +273,8 @@ EXPORTED_SYMBOLS = [
     "dropest_key_width", "dropest_ctx_split", "dropest_shard_matrix_narrow", "dropest_shard_matrix_bytes", "dropest_add_umi_to_cell", "dropest_umi_first_seen", "dropest_resident_reads", "dropest_prefetch_raw_matrix_narrow", "dropest_narrow_matrix_possible", "dropest_count_matrix_csc_narrow",
     "dropest_prefetch_raw_matrix_bytes", "dropest_count_matrix_csc_bytes", "dropest_matrix_bytes_widen", "dropest_matrix_rider_widen", "dropest_set_raw_matrix_prefetch", "dropest_set_matrix_wire", "dropest_set_umi_dictionary", "dropest_debug_refresh", "dropest_push_reads_gather", "dropest_shard_set_umi_qualities", "dropest_shard_set_umi_qualities_var",
     "dropest_debug_poison_scratch", "dropest_debug_trim_pool", "dropest_debug_alloc_ordinal", "dropest_debug_alloc_site",
+    "dropest_set_save_umi_merge_targets", "dropest_umi_merge_targets", "dropest_read_corrections", "dropest_read_corrections_host",
+    "dropest_read_correction_counts",
 ]
 
 
@@ -697,6 +704,42 @@ class Context:
         """pairs: [(source code, target code)] applied in order (Cell::merge_umis walks the caller's map)."""
         s = np.array([p[0] for p in pairs], np.uint64); t = np.array([p[1] for p in pairs], np.uint64)
         self._chk(self.L.dropest_merge_umis(self.h, cell, gene, len(pairs), s.ctypes.data, t.ctypes.data))
+
+    # ---- -F: what the final container made of every read (include/dropest_amd.h) ----
+    def set_save_umi_merge_targets(self, on=True):
+        """The constructor's save_umi_merge_targets: keep Gene::merge_targets().  Before merge_and_filter; off by default."""
+        self._chk(self.L.dropest_set_save_umi_merge_targets(self.h, int(bool(on))))
+
+    def umi_merge_targets(self):
+        """(cell, gene, source code, target code), ascending (cell, gene, source code)."""
+        n = C.c_uint64()
+        self._chk(self.L.dropest_umi_merge_targets(self.h, C.byref(n), None, None, None, None))
+        cell = np.zeros(n.value, np.uint32); gene = np.zeros(n.value, np.uint32)
+        src = np.zeros(n.value, np.uint64); tgt = np.zeros(n.value, np.uint64)
+        if n.value:
+            self._chk(self.L.dropest_umi_merge_targets(self.h, C.byref(n), cell.ctypes.data, gene.ctypes.data, src.ctypes.data, tgt.ctypes.data))
+        return cell, gene, src, tgt
+
+    def read_corrections_device(self):
+        """(n, d_verdict, d_cell, d_umi): raw device pointers, valid until the container changes."""
+        n = C.c_uint64()
+        pv, pc, pu = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        self._chk(self.L.dropest_read_corrections(self.h, C.byref(n), C.byref(pv), C.byref(pc), C.byref(pu)))
+        return n.value, pv.value, pc.value, pu.value
+
+    def read_corrections(self, first=0, count=None):
+        """Host copies (verdict u8, target cell u32, corrected UMI u64) of the decided reads [first, first + count)."""
+        if count is None:
+            count = self.read_corrections_device()[0] - first
+        verdict = np.zeros(count, np.uint8); cell = np.zeros(count, np.uint32); umi = np.zeros(count, np.uint64)
+        self._chk(self.L.dropest_read_corrections_host(self.h, first, count, verdict.ctypes.data, cell.ctypes.data, umi.ctypes.data))
+        return verdict, cell, umi
+
+    def read_correction_counts(self):
+        """Reads per verdict: [written, no gene, cell not kept, wrong gene, wrong UMI]."""
+        out = np.zeros(5, np.uint64)
+        self._chk(self.L.dropest_read_correction_counts(self.h, out.ctypes.data))
+        return out
 
     def add_umi_to_cell(self, cell, gene, umi_code, mark, quality=b""):
         q = np.frombuffer(bytes(quality), np.uint8)

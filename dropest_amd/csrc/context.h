@@ -694,6 +694,23 @@ struct dropest_ctx {
 	void validation_evaluate(const ValidationView &V, const dropest_validation_opts &opts, dropest_validation_sample &S, const std::vector<u32> &a,
 	                         const std::vector<u32> &b);
 	void run_merge_validation(const dropest_validation_opts *opts, dropest_validation_sample *samples, u32 n_samples);
+	// per-read corrected cell barcode and UMI, -F (read_corrections.h).  Gene::merge_targets(): the (source, target) pairs the UMI merges applied,
+	// logged in application order while save_umi_targets is on; umi_merge_target_rows() orders them and keeps the last target of each source
+	bool save_umi_targets = false;
+	struct UmiTargetRow { u32 cell, gene; u64 source, target; };
+	std::vector<UmiTargetRow> umi_targets;
+	bool umi_targets_ordered = true;
+	void record_umi_target(u32 cell, u32 gene, u64 source, u64 target);
+	void record_rekeyed_molecules(const u64 *keys_new, u32 n_changed);
+	const std::vector<UmiTargetRow> &umi_merge_target_rows();
+	// verdict, target cell and corrected UMI of every resident read on the device, kept until the container changes (request_filtered, free_results)
+	struct ReadCorrections {
+		bool valid = false;
+		u32 n = 0;
+		dropest::DevBuf<uint8_t> verdict; dropest::DevBuf<u32> cell; dropest::DevBuf<u64> umi;
+		uint64_t counts[5] = {0, 0, 0, 0, 0};
+	} corrections;
+	void build_read_corrections();
 	void poisson_build_tables(const u32 *d_counts, u32 n_counts, double total, u32 max_size);
 	void poisson_expected_from_keys(const u32 *d_off, u32 NP, const u64 *d_keys, u32 NK, double *expected_host);
 	// sharded -M (merge_shard.h): this shard's dense UMI histogram; the tables from the summed one; expected sizes of pairs with shipped base rows

@@ -286,6 +286,7 @@ void dropest_ctx::free_results() {
 	merge_rank.clear(); reagg_prio = nullptr; extra_excluded.clear(); explicit_sources.clear(); mol_sorted_rows = 0xFFFFFFFFu;
 	layout = dropest::KeyLayout{}; umi_clean_bits = 0; umi_sentinel_stripped = false; chr_from_gene = false;   // nothing of the previous pass's key plan survives
 	umi_dict_on = false; umi_dict_n = 0; umi_dict_host.clear();
+	umi_targets.clear(); umi_targets_ordered = true; corrections.valid = false;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1532,6 +1533,7 @@ void dropest_ctx::request_filtered(u32 genes_threshold, int max_cells) {
 	// the real-cell count is cheap and always current; the ordering is produced when somebody reads it
 	filtered_threshold = genes_threshold; filtered_max_cells = max_cells; filtered_valid = false;
 	strategy_targets = StrategyTargets();
+	corrections.valid = false;
 	n_real_now = 0;
 	constexpr unsigned W = dropest::HostPool::MAX;
 	uint64_t part[W + 1] = {0};   // (2.4e6 rows at C3 size: a millisecond or two for one thread)
@@ -1776,6 +1778,7 @@ void dropest_ctx::sort_filtered(u32 genes_threshold, int max_cells) {
 #include "mutate_host.h"
 #include "matrix_emit.h"
 #include "validation.h"
+#include "read_corrections.h"
 
 // ------------------------------------------------------------------------------------------------
 // top-level stages
@@ -2368,6 +2371,59 @@ dropest_status dropest_merge_umis(dropest_ctx *ctx, uint64_t cell, uint32_t gene
 		if (cell >= ctx->n_cells) throw RangeError("cell index out of range");
 		if (n && (!source_umis || !target_umis)) throw InvalidError("null UMI array");
 		ctx->mutate_merge_umis(u32(cell), gene, n, source_umis, target_umis);
+	});
+}
+
+dropest_status dropest_set_save_umi_merge_targets(dropest_ctx *ctx, int enabled) {
+	return guarded([&] {
+		if (!ctx) throw InvalidError("null context");
+		if (ctx->merged) throw InvalidError("save_umi_merge_targets must be set before merge_and_filter");
+		ctx->save_umi_targets = enabled != 0;
+	});
+}
+
+dropest_status dropest_umi_merge_targets(dropest_ctx *ctx, uint64_t *n, uint32_t *cell, uint32_t *gene, uint64_t *source_umi, uint64_t *target_umi) {
+	return guarded([&] {
+		need_init(ctx);
+		if (!n) throw InvalidError("null argument");
+		const std::vector<dropest_ctx::UmiTargetRow> &rows = ctx->umi_merge_target_rows();
+		*n = rows.size();
+		if (!cell && !gene && !source_umi && !target_umi) return;
+		if (!cell || !gene || !source_umi || !target_umi) throw InvalidError("null argument");
+		for (size_t i = 0; i < rows.size(); ++i) { cell[i] = rows[i].cell; gene[i] = rows[i].gene; source_umi[i] = rows[i].source; target_umi[i] = rows[i].target; }
+	});
+}
+
+dropest_status dropest_read_corrections(dropest_ctx *ctx, uint64_t *n, const uint8_t **d_verdict, const uint32_t **d_cell, const uint64_t **d_umi) {
+	return guarded([&] {
+		if (!ctx || !n || !d_verdict || !d_cell || !d_umi) throw InvalidError("null argument");
+		HIP_CHECK(hipSetDevice(ctx->cfg.device));
+		ctx->build_read_corrections();
+		*n = ctx->corrections.n;
+		*d_verdict = ctx->corrections.verdict.p; *d_cell = ctx->corrections.cell.p; *d_umi = reinterpret_cast<const uint64_t *>(ctx->corrections.umi.p);
+	});
+}
+
+dropest_status dropest_read_corrections_host(dropest_ctx *ctx, uint64_t first, uint64_t count, uint8_t *verdict, uint32_t *cell, uint64_t *umi) {
+	return guarded([&] {
+		if (!ctx) throw InvalidError("null context");
+		HIP_CHECK(hipSetDevice(ctx->cfg.device));
+		ctx->build_read_corrections();
+		const dropest_ctx::ReadCorrections &R = ctx->corrections;
+		if (first > R.n || count > R.n - first) throw RangeError("read ordinal out of range");
+		if (!count) return;
+		if (verdict) ctx->fetch(verdict, R.verdict.p + first, size_t(count));
+		if (cell) ctx->fetch(cell, R.cell.p + first, size_t(count) * 4);
+		if (umi) ctx->fetch(umi, R.umi.p + first, size_t(count) * 8);
+	});
+}
+
+dropest_status dropest_read_correction_counts(dropest_ctx *ctx, uint64_t out[5]) {
+	return guarded([&] {
+		if (!ctx || !out) throw InvalidError("null argument");
+		HIP_CHECK(hipSetDevice(ctx->cfg.device));
+		ctx->build_read_corrections();
+		for (int i = 0; i < 5; ++i) out[i] = ctx->corrections.counts[i];
 	});
 }
 

@@ -125,25 +125,26 @@ void CellsDataContainer::fill_cfg(dropest_cfg &cfg, std::string &levels) const {
 
 CellsDataContainer::CellsDataContainer(const std::shared_ptr<Merge::MergeStrategyAbstract> &merge_strategy,
                                        const std::shared_ptr<Merge::UMIs::MergeUMIsStrategyAbstract> &umi_merge_strategy,
-                                       const std::vector<UMI::Mark> &gene_match_levels, bool /*save_umi_merge_targets*/,
+                                       const std::vector<UMI::Mark> &gene_match_levels, bool save_umi_merge_targets,
                                        int max_cells_num, int device)
 	: _merge_strategy(merge_strategy), _umi_merge_strategy(umi_merge_strategy), _query_marks(gene_match_levels) {
-	_device = device; _max_cells_num = max_cells_num;
+	_device = device; _max_cells_num = max_cells_num; _save_umi_merge_targets = save_umi_merge_targets;
 	dropest_cfg cfg; std::string levels;
 	fill_cfg(cfg, levels);
 	check(dropest_ctx_create(&cfg, &_ctx));
+	check(dropest_set_save_umi_merge_targets(_ctx, _save_umi_merge_targets));
 }
 
 CellsDataContainer::CellsDataContainer(const std::shared_ptr<Merge::MergeStrategyAbstract> &merge_strategy,
                                        const std::shared_ptr<Merge::UMIs::MergeUMIsStrategyAbstract> &umi_merge_strategy,
-                                       const std::vector<UMI::Mark> &gene_match_levels, bool /*save_umi_merge_targets*/,
+                                       const std::vector<UMI::Mark> &gene_match_levels, bool save_umi_merge_targets,
                                        int max_cells_num, const std::vector<int> &devices)
 	: _merge_strategy(merge_strategy), _umi_merge_strategy(umi_merge_strategy), _query_marks(gene_match_levels) {
 	if (devices.empty()) throw std::runtime_error("no device given");
-	_device = devices[0]; _max_cells_num = max_cells_num;
+	_device = devices[0]; _max_cells_num = max_cells_num; _save_umi_merge_targets = save_umi_merge_targets;
 	dropest_cfg cfg; std::string levels;
 	fill_cfg(cfg, levels);
-	if (devices.size() == 1) { check(dropest_ctx_create(&cfg, &_ctx)); return; }
+	if (devices.size() == 1) { check(dropest_ctx_create(&cfg, &_ctx)); check(dropest_set_save_umi_merge_targets(_ctx, _save_umi_merge_targets)); return; }
 	std::vector<int32_t> dev(devices.begin(), devices.end());
 	_shards.assign(devices.size(), nullptr);
 	_shard_devices = devices;
@@ -167,6 +168,7 @@ dropest_ctx *CellsDataContainer::view() const {
 	dropest_cfg cfg; std::string levels;
 	fill_cfg(cfg, levels);
 	check(dropest_ctx_create(&cfg, &_preview));
+	check(dropest_set_save_umi_merge_targets(_preview, _save_umi_merge_targets));
 	send_side_strings(_preview);
 	const uint64_t *cb = nullptr, *umi = nullptr; const uint32_t *gene = nullptr, *aux = nullptr; uint64_t n = 0;
 	check(dropest_resident_reads(_ctx, &cb, &umi, &gene, &aux, &n));
@@ -728,6 +730,20 @@ void CellsDataContainer::merge_umis(size_t cell_id, size_t gene, const s_s_hash_
 	apply_mutation(view(), m);
 	if (!_is_initialized) _pending.push_back(m);
 	++_generation;
+}
+
+CellsDataContainer::s_s_hash_t CellsDataContainer::umi_merge_targets(size_t cell_id, size_t gene) const {   // Gene::merge_targets(), Gene.cpp:124-127
+	if (sharded()) single_only("umi_merge_targets");
+	dropest_ctx *ctx = view();
+	uint64_t n = 0;
+	check(dropest_umi_merge_targets(ctx, &n, nullptr, nullptr, nullptr, nullptr));
+	std::vector<uint32_t> cells(n), genes(n);
+	std::vector<uint64_t> src(n), tgt(n);
+	if (n) check(dropest_umi_merge_targets(ctx, &n, cells.data(), genes.data(), src.data(), tgt.data()));
+	s_s_hash_t out;
+	for (uint64_t i = 0; i < n; ++i)
+		if (cells[i] == cell_id && genes[i] == gene) out.emplace(decode(src[i]), decode(tgt[i]));
+	return out;
 }
 
 long CellsDataContainer::get_merge_target(size_t base_cell_ind) const {

@@ -335,6 +335,7 @@ private:
 	mutable bool _preview_valid = false;
 	int _device = 0;
 	int _max_cells_num = -1;
+	bool _save_umi_merge_targets = false;                      // Gene::_save_merge_targets: every context of this container gets it
 	void fill_cfg(dropest_cfg &cfg, std::string &levels) const;
 	dropest_ctx *view() const;                                 // the context accessors read: the real one, or the preview
 	void apply_mutation(dropest_ctx *ctx, const PendingMutation &m);
@@ -489,6 +490,10 @@ public:
 	void exclude_cell(size_t index);
 	void merge_cells(size_t source_cell_ind, size_t target_cell_ind);
 	void merge_umis(size_t cell_id, size_t gene, const s_s_hash_t &merge_targets);                  // RealBarcodesMergeStrategy::get_merge_target
+	// cell(cell_id).genes().at(gene).merge_targets() (Gene.h; Gene.cpp:54-57, :124-127): {source UMI: target UMI} of the UMI merges applied to
+	// that gene of that cell; empty unless the container was made with save_umi_merge_targets (one GPU: the sharded container ignores the flag)
+	s_s_hash_t umi_merge_targets(size_t cell_id, size_t gene) const;
+	bool save_umi_merge_targets() const { return _save_umi_merge_targets; }
 	// CellsDataContainer.h:90 (CellsDataContainer.cpp:356-364): one more read of read_info's UMI for read_info's gene in cell
 	// `cell_id` -- a new molecule (TOTAL_UMIS_PER_CB + 1) or read count + 1 / mark OR; no read counters, no chromosome statistics.
 	// Cell ids exist once the container is initialised (they are assigned on the device): std::runtime_error before that.

@@ -111,6 +111,7 @@ void dropest_ctx::mutate_merge_umis(u32 cell, u32 gene, uint64_t n, const uint64
 	u64 or_and[2];
 	fetch(or_and, d_or_and, 16);
 	reaggregate_from_keys(or_and[0] ^ or_and[1]);
+	for (uint64_t i = 0; i < n; ++i) record_umi_target(cell, gene, src[i], tgt[i]);   // Gene::_merge_targets (Gene.cpp:54-57), in the caller's order
 	real_pristine = false;
 	real[size_t(ri)].row.total_umis -= removed;
 	request_filtered(filtered_threshold, filtered_max_cells);

@@ -152,6 +152,7 @@ void dropest_ctx::run_umi_merge_directional() {
 
 	std::unordered_map<u32, int> umis_removed;
 	if (n_changed) {
+		record_rekeyed_molecules(keys_a.p, n_changed);   // Gene::merge_targets() of the groups decided on the device (read_corrections.h)
 		// TOTAL_UMIS decrements of the real cells (Cell::merge_umis, Cell.cpp:31-42)
 		const u32 nr = u32(real.size());
 		std::vector<u32> ids(nr), rem(nr);
@@ -243,6 +244,16 @@ void dropest_ctx::run_umi_merge_directional() {
 			else { it->second.reads += moved.reads; it->second.mark |= moved.mark; }
 			merged.erase(t.first);
 			umis_removed[cell] += 1;
+			if (save_umi_targets) {   // Gene::_merge_targets[source] = target (Gene.cpp:54-57)
+				auto code = [&](const std::string &seq) {
+					u64 c;
+					auto known = code_of.find(seq);
+					if (known != code_of.end()) return known->second;
+					if (!encode_code(seq, c)) throw UnsupportedError("re-keyed UMI does not fit a 2-bit code: " + seq);
+					return c;
+				};
+				record_umi_target(cell, u32((GG.hk[GG.off[g]] >> layout.umi_bits) & layout.gene_none), code(t.first), code(t.second));
+			}
 		}
 		std::vector<UmiOverride> ov;
 		u32 n_req = 0, reads_req = 0;

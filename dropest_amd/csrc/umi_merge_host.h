@@ -336,6 +336,13 @@ void dropest_ctx::run_umi_merge_simple() {
 			if (it == merged.end()) merged[t.second] = Folded{src.reads, src.mark, src.row};   // copy of the source (Gene.cpp:49)
 			else { it->second.reads += src.reads; it->second.mark |= src.mark; }
 			umis_removed[cell] += 1;
+			if (save_umi_targets) {   // Gene::_merge_targets[source] = target (Gene.cpp:54-57)
+				u64 tcode;
+				auto known = code_of.find(t.second);
+				if (known != code_of.end()) tcode = known->second;
+				else if (!encode_code(t.second, tcode)) throw UnsupportedError("re-keyed UMI does not fit a 2-bit code: " + t.second);
+				record_umi_target(cell, u32((hk[off[g]] >> layout.umi_bits) & layout.gene_none), src.code, tcode);
+			}
 		}
 		std::vector<UmiOverride> ov;
 		u32 n_req = 0, reads_req = 0;

@@ -183,6 +183,41 @@ dropest_status dropest_exclude_cell(dropest_ctx *ctx, uint64_t cell);
 dropest_status dropest_merge_cells(dropest_ctx *ctx, uint64_t source_cell, uint64_t target_cell);
 dropest_status dropest_merge_umis(dropest_ctx *ctx, uint64_t cell, uint32_t gene, uint64_t n, const uint64_t *source_umis,
                                   const uint64_t *target_umis);
+
+/* ---- what the final container made of every read: `dropest -F` (BamController::write_filtered_bam_files ->
+ * FilteringBamProcessor::write_alignment, Estimation/BamProcessing/FilteringBamProcessor.cpp:14-40, :61-96) ----
+ * The pushed reads stay resident after merge_and_filter; read i of the stream is the i-th record a BAM reader accepted.
+ *
+ * dropest_set_save_umi_merge_targets: the constructor's save_umi_merge_targets (CellsDataContainer.h:82-85 -> Gene::Gene, Gene.cpp:7-10).
+ * Off by default, as in the reference; set it before dropest_merge_and_filter (after it: DROPEST_ERR_INVALID).  A setting of the context:
+ * it survives dropest_reset_results / dropest_clear_reads.  While it is on, every pair (source, target) that a UMI merge applies -- the
+ * Simple and the directional strategy, and dropest_merge_umis -- is kept as Gene::merge(source, target) keeps it (Gene.cpp:54-57): one hop
+ * per (cell, gene), the last assignment of a source wins, pairs with source == target are not kept.  The barcode merge does not move the
+ * pairs of a cell it folds into another (Gene::merge(const Gene &), Gene.cpp:26-36); the strategies' UMI merges run after it
+ * (CellsDataContainer.cpp:44-46), so theirs belong to final cells.  dropest_reset_results drops them.
+ * dropest_umi_merge_targets: Gene::merge_targets() of all genes of all cells, ascending (cell, gene, source code); UMIs in the packed /
+ * escaped form of the way in; null arrays give *n. */
+dropest_status dropest_set_save_umi_merge_targets(dropest_ctx *ctx, int enabled);
+dropest_status dropest_umi_merge_targets(dropest_ctx *ctx, uint64_t *n, uint32_t *cell, uint32_t *gene, uint64_t *source_umi,
+                                         uint64_t *target_umi);
+/* The decision of FilteringBamProcessor::write_alignment for every resident read, in stream order, on the state the container is in now
+ * (after merge_and_filter: the state write_filtered_bam_files sees; before it, every cell is its own merge target).  Three DEVICE arrays of
+ * *n entries, owned by the context and valid until the container changes (a mutator, merge_and_filter, reset, clear):
+ *   verdict  0 written; 1 the read has no gene (:63-64); 2 the merge target of its barcode's cell is not a filtered cell (:22-37, :66-68);
+ *            3 that cell has no such gene (:70-76, _wrong_genes); 4 the gene has the read's UMI neither as a merge source nor as a
+ *            molecule (:88-92, _wrong_umis)
+ *   cell     id of the target cell, whose barcode is the corrected CB (verdicts 0, 3, 4; 0xFFFFFFFF for 1 and 2)
+ *   umi      verdict 0: the corrected UB -- the merge target of the read's UMI when Gene::merge_targets() has it as a source (one hop, not
+ *            looked up among the molecules, and before the next test, :79-83), else the read's own UMI, which is then a molecule of the
+ *            gene (:84-87); any other verdict: the read's own UMI.  Packed / escaped as on the way in.
+ * With save_umi_merge_targets off the reads of merged-away UMIs get verdict 4, as in the reference.  Refused (DROPEST_ERR_UNSUPPORTED): a
+ * shard's context, a context dropest_ctx_split emptied, a pass in UMI-dictionary mode (dropest_set_umi_dictionary).
+ * dropest_read_corrections_host copies entries [first, first + count) to host arrays (any may be null);
+ * dropest_read_correction_counts gives the number of reads per verdict (out[0] = _written_reads, out[3] = _wrong_genes, out[4] = _wrong_umis). */
+dropest_status dropest_read_corrections(dropest_ctx *ctx, uint64_t *n, const uint8_t **d_verdict, const uint32_t **d_cell,
+                                        const uint64_t **d_umi);
+dropest_status dropest_read_corrections_host(dropest_ctx *ctx, uint64_t first, uint64_t count, uint8_t *verdict, uint32_t *cell, uint64_t *umi);
+dropest_status dropest_read_correction_counts(dropest_ctx *ctx, uint64_t out[5]);
 /* CellsDataContainer::add_umi_to_cell (CellsDataContainer.h:90, CellsDataContainer.cpp:356-364) on the initialised container:
  * one more read of `umi_code` (packed as on the way in) for gene index `gene` in cell `cell` with mark bits `mark` --
  * Gene::add_umi: a new molecule (TOTAL_UMIS_PER_CB + 1) or read_count + 1 / mark OR of the existing one; like the reference's
