@@ -1,5 +1,7 @@
 // bam_device.cpp -- the device path of BamController::parse_bam_files (bam_ingest.h; include/dropest_bgzf.h; DROPEST_BAM_DEVICE=1 or
 // BamController::set_device_decode).
+// The decoder behind that header: csrc/bam_decoder.h, bam_decoder_dict.h, bam_decoder_upload.h, bam_decoder_window.h, bam_decoder_fetch.h and bam_decoder_tag.h, compiled as parts of
+// csrc/bgzf_api.hip; the block table it takes from this file's walks is bgzf::BlockTable (bgzf_blocks.h).
 // The blocks are inflated on the GPU (csrc/k_inflate.h: a wave per block), the chain of records is found and every record's tags
 // are walked there (csrc/k_bamparse.h: a lane per record); 39 bytes per record come back instead of the ~300 of the record.  The
 // dictionaries stay here: the workers turn gene hashes and reference ids into indices, and the records that bring something NEW

@@ -1,6 +1,7 @@
 // bgzf_blocks.h -- where the BGZF blocks of a BAM file are (SAMv1 §4.1): one parse of a block's header, and the walks over it that the host
 // reader (bam_ingest.cpp) and the device path (bam_device.cpp) make.  Host-only, no library behind it: the walks differ in what they take
-// for an error and say so themselves; the header is read in one place.  Nothing here reads the environment.
+// for an error and say so themselves; the header is read in one place.  Also the walk of the C-ABI (scan_blocks: dropest_bgzf_scan) and the block
+// table of the device decoder (BlockTable), which csrc/bgzf_api.hip includes from here.  Nothing here reads the environment.
 #pragma once
 
 #include <unistd.h>
@@ -88,6 +89,81 @@ struct Blocks {
 	void append(const Blocks &o) {
 		in_off.insert(in_off.end(), o.in_off.begin(), o.in_off.end()); in_len.insert(in_len.end(), o.in_len.begin(), o.in_len.end());
 		out_len.insert(out_len.end(), o.out_len.begin(), o.out_len.end()); crc.insert(crc.end(), o.crc.begin(), o.crc.end());
+	}
+};
+
+// The walk of the C-ABI (dropest_bgzf_scan) over data[0 .. len): whole, sound blocks into the caller's arrays (crc may be null), at most cap of
+// them; a block that is cut off ends the walk without a word.  Returns what is wrong ("": nothing), and writes n / used / total only then.
+// (as strict as walk_blocks, and the only walk that says where: the offset of the block's first byte)
+inline std::string scan_blocks(const uint8_t *data, uint64_t len, uint64_t cap, uint64_t *in_off, uint32_t *in_len, uint64_t *out_off, uint32_t *out_len,
+                               uint32_t *crc, uint64_t &n_blocks, uint64_t &used, uint64_t &out_total) {
+	uint64_t at = 0, n = 0, total = 0;
+	while (n < cap && at + 18 <= len) {
+		const Header hd = parse_header(data + at, size_t(len - at));
+		if (!hd.magic_ok) return "not a BGZF block header at offset " + std::to_string(at);
+		if (!hd.header_complete) break;
+		if (!hd.bsize || hd.bsize < 12 + hd.xlen + 8) return "BGZF block without a BC subfield at offset " + std::to_string(at);
+		if (at + hd.bsize > len) break;
+		const uint8_t *const tail = data + at + hd.bsize - 8;
+		in_off[n] = at + 12 + hd.xlen; in_len[n] = uint32_t(hd.bsize - 12 - hd.xlen - 8);
+		out_off[n] = total; out_len[n] = le32(tail + 4);
+		if (out_len[n] > 65536u) return "BGZF block with ISIZE beyond 64 KB at offset " + std::to_string(at);
+		if (crc) crc[n] = le32(tail);
+		total += out_len[n];
+		at += hd.bsize; ++n;
+	}
+	n_blocks = n; used = at; out_total = total;
+	return std::string();
+}
+
+// The block table of a window as the device's inflate and the host fall-back take it: five arrays of one capacity (kept from window to window),
+// offsets in relative to the window's compressed bytes, offsets out to its inflated ones.
+struct BlockTable {
+	std::vector<uint64_t> in_off, out_off; std::vector<uint32_t> in_len, out_len, crc;
+	uint64_t n = 0, used = 0, total = 0;
+	bool ok = false;
+	std::string error;      // !ok: what scan_blocks said
+
+	void grow(uint64_t cap) {
+		if (in_off.size() >= cap) return;
+		const uint64_t c2 = cap + cap / 2;
+		in_off.resize(c2); out_off.resize(c2); in_len.resize(c2); out_len.resize(c2); crc.resize(c2);
+	}
+	void swap(BlockTable &o) {
+		in_off.swap(o.in_off); out_off.swap(o.out_off); in_len.swap(o.in_len); out_len.swap(o.out_len); crc.swap(o.crc);
+		std::swap(n, o.n); std::swap(used, o.used); std::swap(total, o.total); std::swap(ok, o.ok); error.swap(o.error);
+	}
+	// comp[0 .. len) walked from block header to block header.  !ok: not whole, sound blocks
+	bool fill(const uint8_t *comp, uint64_t len) {
+		// counted first: arrays for the smallest possible block, 26 bytes, would be 36 MB of page faults per 32 MB window
+		uint64_t cap = 1;
+		for (uint64_t at = 0; at + 18 <= len; ++cap) {
+			const Header hd = parse_header(comp + at, size_t(len - at));
+			if (!hd.magic_ok || !hd.bsize) break;                      // (scan_blocks says what is wrong)
+			at += hd.bsize;
+		}
+		grow(cap);
+		n = used = total = 0;
+		error = len ? scan_blocks(comp, len, cap, in_off.data(), in_len.data(), out_off.data(), out_len.data(), crc.data(), n, used, total) : std::string();
+		return ok = error.empty();
+	}
+	// A table the caller made while it read the file (block k: payload at c_in_off[k], c_in_len[k] bytes, ISIZE c_out_len[k], CRC-32 c_crc[k]),
+	// checked for what the kernel relies on: blocks in order with room for a header in front of each, the last one ending at len, no ISIZE beyond
+	// 64 KB.  A table that is not given (a null array, no block) or not sound: the walk over host[0 .. len) decides.
+	bool fill(uint64_t c_n, const uint64_t *c_in_off, const uint32_t *c_in_len, const uint32_t *c_out_len, const uint32_t *c_crc, const uint8_t *host, uint64_t len) {
+		ok = false;
+		if (c_n && c_in_off && c_in_len && c_out_len && c_crc) {
+			grow(c_n);
+			uint64_t sum = 0, at = 0;
+			bool sound = true;
+			for (uint64_t k = 0; k < c_n && sound; ++k) {
+				sound = c_in_off[k] >= at + 18 && c_in_off[k] + c_in_len[k] + 8 <= len && c_out_len[k] <= 65536u;
+				in_off[k] = c_in_off[k]; in_len[k] = c_in_len[k]; out_off[k] = sum; out_len[k] = c_out_len[k]; crc[k] = c_crc[k];
+				sum += c_out_len[k]; at = c_in_off[k] + c_in_len[k] + 8;
+			}
+			if (sound && at == len) { n = c_n; used = len; total = sum; error.clear(); return ok = true; }
+		}
+		return fill(host, len);
 	}
 };
 

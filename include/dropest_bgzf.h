@@ -36,7 +36,7 @@ int dropest_bgzf_inflate_device(int device, void *stream, const uint8_t *d_in, u
 int dropest_bgzf_inflate_buffer(int device, const uint8_t *data, uint64_t len, uint8_t *out, uint64_t out_cap, uint64_t *out_len,
                                 uint32_t *status, uint64_t status_cap, uint64_t *n_blocks, double *kernel_ms, int repeats);
 
-/* ---- BAM records of a window of BGZF blocks, on the device (csrc/k_bamparse.h) -------------------------------------------------------
+/* ---- BAM records of a window of BGZF blocks, on the device (csrc/k_bamparse.h; csrc/bam_decoder*.h) -------------------------------------------------------
  * What BamController::process_alignment (BamController.cpp:132-172) decides without a dictionary: the reader's status of a record, the
  * 2-bit codes of its barcode and UMI, its UMI::Mark, and -- against a copy of the caller's dictionaries -- its gene and chromosome index:
  * the accepted records leave as the four dense columns of dropest_push_reads IN DEVICE MEMORY (dropest_push_reads_device takes them as
@@ -157,7 +157,7 @@ int dropest_bam_decoder_quality_rows(dropest_bam_decoder *d, uint32_t ql, const 
 int dropest_bam_decoder_patch(dropest_bam_decoder *d, const uint32_t *pos, const uint64_t *cb, const uint64_t *umi, const uint32_t *gene,
                               const uint32_t *aux, uint32_t n);
 
-/* ---- -b: tagged BAM output (csrc/k_bamtag.h; DESIGN.md section 7 has the edit rule) ---------------------------------------------------
+/* ---- -b: tagged BAM output (csrc/k_bamtag.h, csrc/bam_decoder_tag.h; DESIGN.md section 7 has the edit rule) ---------------------------------------------------
  * What BamProcessorAbstract::save_alignment (BamProcessorAbstract.cpp:65-114) writes for every accepted alignment: the record with its gene, raw
  * barcode, raw UMI, the two quality strings and the read type as Z tags.  Every aux entry the tag walk reaches whose name is one of the edited
  * names is left out (every occurrence, whatever its type); the edited tags are appended in the order gene, raw barcode, raw UMI, barcode quality,

@@ -8,6 +8,12 @@
 //   walk FROM START UNTIL AVAIL MAX                FileWalk{file_at = FROM}.walk_blocks(START, UNTIL, AVAIL, MAX)
 //   wbf FROM AVAIL WANT CAP AVG BYTES BLOCKS ONE   FileWalk{...}.whole_blocks_of_file(AVAIL, WANT)
 //   hdr FROM N                                     parse_header(FILE + FROM, N): magic_ok,header_complete,xlen,bsize,bsize_cut in the error column
+//   tab SIZE FROM                                  BlockTable::fill(FILE + FROM, SIZE - FROM): o = used, the stretched column = ok, the error column =
+//                                                  the table's error or "n=N,total=T"; the table with a fifth number per block, its offset out
+//   cal SIZE FROM HOW                              the same through BlockTable::fill(a caller's table, FILE + FROM, SIZE - FROM): the caller's table is
+//                                                  the walk's own with every CRC + 1 (so that a table taken from the caller shows), and HOW spoils it:
+//                                                  good | gap (block 1 left out) | overlap (block 1 begins inside block 0) | short (the last block left
+//                                                  out) | big (block 1 with ISIZE 65537) | null (no CRC array)
 #include "../../dropest_amd/csrc/host/bgzf_blocks.h"
 
 #include <fcntl.h>
@@ -23,6 +29,12 @@ static std::string table_of(const Blocks &B, size_t base) {
 	std::ostringstream s;
 	for (size_t k = 0; k < B.in_off.size(); ++k) s << base + B.in_off[k] << ',' << B.in_len[k] << ',' << B.out_len[k] << ',' << B.crc[k] << ';';
 	return s.str();
+}
+static void answer_of(const BlockTable &T, size_t base, size_t &o, bool &ok, std::string &error, std::string &table) {
+	std::ostringstream s, e;
+	for (size_t k = 0; k < T.n; ++k) s << base + T.in_off[k] << ',' << T.in_len[k] << ',' << T.out_len[k] << ',' << T.crc[k] << ',' << T.out_off[k] << ';';
+	e << "n=" << T.n << ",total=" << T.total;
+	o = T.used; ok = T.ok; error = T.ok ? e.str() : T.error; table = s.str();
 }
 static size_t num(std::istream &in) { long long v = 0; in >> v; return v < 0 ? size_t(-1) : size_t(v); }
 
@@ -75,6 +87,29 @@ int main(int argc, char **argv) {
 				o = w.whole_blocks_of_file(avail, want, B, error, &stretched);
 			}
 			table = table_of(B, w.file_at);
+		} else if (cmd == "tab" || cmd == "cal") {
+			const size_t size = num(in), from = num(in);
+			std::vector<uint8_t> copy(bytes.begin() + from, bytes.begin() + size);      // (exactly the bytes given: a read beyond them is the sanitizer's to see)
+			BlockTable T;
+			T.n = T.used = T.total = 77;      // (what a table kept from the window before holds)
+			if (cmd == "tab") T.fill(copy.data(), copy.size());
+			else {
+				std::string how;
+				in >> how;
+				BlockTable W;
+				if (!W.fill(copy.data(), copy.size()) || W.n < 3) return 2;
+				std::vector<uint64_t> c_off(W.in_off.begin(), W.in_off.begin() + W.n);
+				std::vector<uint32_t> c_len(W.in_len.begin(), W.in_len.begin() + W.n), c_out(W.out_len.begin(), W.out_len.begin() + W.n), c_crc(W.crc.begin(), W.crc.begin() + W.n);
+				for (uint32_t &c : c_crc) c += 1;
+				auto drop = [&](size_t k) { c_off.erase(c_off.begin() + k); c_len.erase(c_len.begin() + k); c_out.erase(c_out.begin() + k); c_crc.erase(c_crc.begin() + k); };
+				if (how == "gap") drop(1);
+				else if (how == "overlap") { c_off[1] = c_off[0] + c_len[0] + 8 + 17; c_len[1] += 1; }      // (one byte short of the room a header takes; the block still ends where it did)
+				else if (how == "short") drop(c_off.size() - 1);
+				else if (how == "big") c_out[1] = 65537;
+				else if (how != "good" && how != "null") return 2;
+				T.fill(c_off.size(), c_off.data(), c_len.data(), c_out.data(), how == "null" ? nullptr : c_crc.data(), copy.data(), copy.size());
+			}
+			answer_of(T, from, o, stretched, error, table);
 		} else if (cmd == "hdr") {
 			const size_t from = num(in), n = num(in);
 			std::vector<uint8_t> copy(bytes.begin() + from, bytes.begin() + from + n);

@@ -2,7 +2,8 @@
 device path), whole_blocks over bytes in memory, FileWalk::walk_blocks / whole_blocks_of_file through pread (the device path's window reader, with
 the four stretches).  All four read a block's header with one parse_header and keep verdicts of their own; tests/cpp/test_bgzf_blocks.cpp is
 compiled with the header alone (address and undefined-behaviour sanitizers, where the compiler has them) and answers a script of calls, and every
-answer is compared with the block table this file reads from the BAM file itself, or with the error text that caller gives."""
+answer is compared with the block table this file reads from the BAM file itself, or with the error text that caller gives.  The same for the
+device decoder's table (BlockTable: filled from bytes by the walk of dropest_bgzf_scan, or from a caller's table that is checked first)."""
 import os
 import struct
 import subprocess
@@ -250,3 +251,100 @@ def test_parse_header_reads_within_its_bytes(exe, tmp_path):
     open(path, "wb").write(b"\x1f\x8b\x08\x04" + bytes(6) + struct.pack("<H", 4) + b"BC" + struct.pack("<HH", 2, 99) + bytes(8))
     a = [r[2] for r in ask(exe, path, ["hdr 0 %d" % n for n in (0, 11, 12, 15, 16, 17, 18, 26)])]
     assert a == ["0,0,0,0,0", "0,0,0,0,0", "1,0,4,0,0", "1,0,4,0,0", "1,1,4,0,0", "1,1,4,0,0", "1,1,4,0,100", "1,1,4,0,100"]
+
+
+# ---- BlockTable: the table of the device path (dropest_bgzf_scan, the decoder's windows and uploads) --------------------------------------
+def table5(blocks):
+    """(offset of the deflate stream, its length, ISIZE, CRC, offset out) as BlockTable holds them"""
+    out, total = [], 0
+    for b in blocks:
+        out.append(b[2:] + (total,))
+        total += b[4]
+    return out
+
+
+def filled(blocks, end=None):
+    """the answer for whole, sound blocks: used, ok, "n=..,total=..", the table"""
+    return (blocks[-1][1] if end is None and blocks else end or 0, 1, "n=%d,total=%d" % (len(blocks), sum(b[4] for b in blocks)), table5(blocks))
+
+
+def test_block_table_from_bytes(exe, good, tmp_path):
+    path, blocks = good["b3"]
+    size = blocks[-1][1]
+    eof = blocks[-1]
+    assert eof[1] - eof[0] == 28 and eof[4] == 0                      # the 28 bytes that end a file
+    k = len(blocks) // 2
+    cuts = [blocks[k][0] + c for c in (1, 11, 12, 17)] + [blocks[k][2], blocks[k][2] + 1, blocks[k][1] - 9, blocks[k][1] - 1]      # inside the 18 header bytes, inside the payload and the trailer
+    answers = ask(exe, path, ["tab 0 0", "tab %d %d" % (size, eof[0]), "tab %d 0" % size, "tab %d %d" % (size, blocks[k][0])] + ["tab %d 0" % c for c in cuts])
+    assert answers[0] == (0, 1, "n=0,total=0", [])                    # no byte: no block, and nothing wrong
+    assert answers[1] == (28, 1, "n=1,total=0", [eof[2:] + (0,)])
+    assert answers[2] == filled(blocks)
+    assert answers[3] == filled(blocks[k:], size - blocks[k][0])      # from a block inside the file: offsets out begin at 0 (offsets in: the program adds FROM)
+    for a in answers[4:]:                                             # a block that is cut off ends the table without a word: `used` says how far it reaches
+        assert a == filled(blocks[:k])
+    # an extra subfield in front of BC, an extra field beyond 64 bytes
+    for name in ("two_subfields", "long_extra"):
+        path, blocks = good[name]
+        assert ask(exe, path, ["tab %d 0" % blocks[-1][1]]) == [filled(blocks)]
+
+
+def bc_beyond_xlen(data):
+    """XLEN 4: the BC subfield's two data bytes are the first two of what follows the extra field"""
+    b = extra_block(BC)(data)
+    return b[:10] + struct.pack("<H", 4) + b[12:]
+
+
+def isize(v):
+    return lambda data: extra_block(BC)(data)[:-4] + struct.pack("<I", v)
+
+
+BAD_TABLE = {  # the third block -> what dropest_bgzf_scan says of it (%d: the offset of the block's first byte)
+    "bc_of_four": (BC_OF_FOUR, "BGZF block without a BC subfield at offset %d"),
+    "no_bc": (NO_BC, "BGZF block without a BC subfield at offset %d"),
+    "bc_beyond_xlen": (bc_beyond_xlen, "BGZF block without a BC subfield at offset %d"),
+    "small_bc": (SMALL_BC, "BGZF block without a BC subfield at offset %d"),
+    "isize_65537": (isize(65537), "BGZF block with ISIZE beyond 64 KB at offset %d"),
+    "bad_magic": (bad_magic, "not a BGZF block header at offset %d"),
+}
+
+
+@pytest.mark.parametrize("name", list(BAD_TABLE))
+def test_block_table_of_malformed_blocks(exe, tmp_path, name):
+    special, error = BAD_TABLE[name]
+    path = str(tmp_path / (name + ".bam"))
+    write_bam(path, REFS, records(300), block=997, compress=only_block(2, special))
+    size = os.path.getsize(path)
+    two = blocks_of_prefix(path, 2)
+    at = two[-1][1]
+    header = 12 + struct.unpack_from("<H", open(path, "rb").read(), at + 10)[0]
+    whole, inside, before = ask(exe, path, ["tab %d 0" % size, "tab %d 0" % (at + max(header, 18)), "tab %d 0" % (at + max(header, 18) - 1)])
+    assert whole == (0, 0, error % at, [])                            # nothing of a window with such a block is kept
+    assert inside == (filled(two) if name == "isize_65537" else whole)      # (judged by its trailer: the header alone is a block cut off)
+    assert before == filled(two)                                      # the header not whole, or fewer than 18 bytes of it: a block cut off
+
+
+def test_block_table_takes_isize_65536(exe, tmp_path):
+    path = str(tmp_path / "isize.bam")
+    write_bam(path, REFS, records(300), block=997, compress=only_block(2, isize(65536)))
+    raw = open(path, "rb").read()
+    (used, ok, said, got), = ask(exe, path, ["tab %d 0" % len(raw)])
+    assert (used, ok) == (len(raw), 1) and got[2][2] == 65536 and got[3][4] == got[2][4] + 65536
+
+
+def test_block_table_from_a_callers_table(exe, good):
+    """A sound table is taken as it is (the CRCs the program made up show it); one that is not -- blocks that overlap, a last block short of the
+    bytes' end, an ISIZE beyond 64 KB, an array missing -- leaves the walk to decide, whose table is the file's.  What is checked is what the
+    kernel relies on (room for a header in front of each block, ends within the bytes): a block left out in the middle is no offence."""
+    path, blocks = good["b997"]
+    size = blocks[-1][1]
+    answers = dict(zip(("good", "gap", "overlap", "short", "big", "null"), ask(exe, path, ["cal %d 0 %s" % (size, how) for how in ("good", "gap", "overlap", "short", "big", "null")])))
+    plus_one = lambda rows: [r[:3] + ((r[3] + 1) & 0xFFFFFFFF,) + r[4:] for r in rows]
+    assert answers["good"] == filled(blocks)[:3] + (plus_one(table5(blocks)),)
+    left_out = blocks[:1] + blocks[2:]
+    assert answers["gap"] == (size, 1, "n=%d,total=%d" % (len(left_out), sum(b[4] for b in left_out)), plus_one(table5(left_out)))
+    for how in ("overlap", "short", "big", "null"):
+        assert answers[how] == filled(blocks), how
+    # ... and from a block inside the file, as a window begins
+    at = blocks[5][0]
+    (used, ok, said, got), = ask(exe, path, ["cal %d %d short" % (size, at)])
+    assert (used, ok, got) == (size - at, 1, table5(blocks[5:]))

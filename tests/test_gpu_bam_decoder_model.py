@@ -306,7 +306,8 @@ def collect(L, dec, w):
         assert L.dropest_bam_decoder_quality_rows(dec, ql, C.byref(p)) == 0, L.dropest_bgzf_last_error()
         rows = np.ctypeslib.as_array(C.cast(p, P(C.c_uint8)), (n, ql)).copy()
     info = dict(n_records=int(w.n_records), counts=list(w.counts), need=need, quality_seen=int(w.quality_seen), any_gene=int(w.any_gene),
-                ql=(int(w.quality_len_min), int(w.quality_len_max)), refused=int(w.refused_blocks), repaired=int(w.guesses_repaired), tail=int(w.tail_bytes))
+                ql=(int(w.quality_len_min), int(w.quality_len_max)), refused=int(w.refused_blocks), repaired=int(w.guesses_repaired), tail=int(w.tail_bytes),
+                blocks=int(w.n_blocks), bytes=int(w.window_bytes))
     return (info, (cb, umi, gene, aux), fetched, rows)
 
 
@@ -418,6 +419,95 @@ def test_layouts_long_records_and_fake_chains(tmp_path):
                 assert any(tails[k] > (1 << 20) and tails[k] > (tails[k - 1] if k else 0) for k in range(len(tails) - 1)), tails
         finally:
             L.dropest_bam_decoder_destroy(dec)
+
+
+class BamFileByBlocks(BamFile):
+    def windows(self, per):
+        """windows of per[0], per[1], ... BLOCKS in turn (the last entry again and again)"""
+        out, k = [], self.b0
+        for j in range(len(self.blocks)):
+            if k >= len(self.blocks):
+                break
+            last = min(k + per[min(j, len(per) - 1)], len(self.blocks))
+            out.append((self.blob[self.blocks[k][0]:self.blocks[last - 1][1]], self.blocks[last - 1][3]))
+            k = last
+        return out
+
+
+def _window_shapes(f, per, rows):
+    """per window of f.windows(per), from the file and the model alone: (blocks, bytes with the record carried over, 16 KB segments of those
+    bytes, records, records the host must see)"""
+    out, k, at, start = [], f.b0, 0, f.blocks[f.b0][2]
+    for comp, end in f.windows(per):
+        n_blocks = 0
+        while k < len(f.blocks) and f.blocks[k][3] <= end:
+            n_blocks += 1; k += 1
+        carried = start - (int(f.ends[at - 1]) if at else start)          # the record the window before cut off
+        upto = int(np.searchsorted(f.ends, end, side="right"))
+        data = carried + end - start
+        out.append((n_blocks, data, -(-data // 16384), upto - at, len(bm.window(rows[at:upto]).need_rec)))
+        at, start = upto, end
+    return out
+
+
+def test_windows_at_the_copy_launches_edges(tmp_path):
+    """The block table goes to the device, the chain's three arrays and the need lists come back, by kernels of 256 lanes a workgroup over n
+    blocks / segments / listed records: windows with n = 1, 256 and 257 of each, with no listed record, and one with no record at all (nothing
+    but the middle of a long record, which the window before and this one carry on).  File A: blocks of 512 bytes, windows of 1, 256 and 257
+    blocks, in which 1, 256 and 257 records name a gene the dictionary does not have ("half": G1 is not in it, G0 is); a record of 3 000 bytes
+    behind them.  File B: blocks of 16 KB, windows of 256 blocks: 256 segments in the first, 257 with the record carried into the second."""
+    L = lib()
+    cfg = dict(CASES)["f-q0-both-Q"]
+    dicts, pairs, names = dictionaries("half")
+    rec = lambda i, gene, seq="ACGT" * 10, extra=(): bw.record(0, i, "r%06d" % i, seq=seq, tags=[("CB", "Z", "ACGTACGTACGT"), ("UB", "Z", "ACGTAC"), ("GX", "Z", gene)] + list(extra))
+    # A: the layout first (every gene known), then the same bytes with the genes of the chosen records changed -- names of one length
+    n_a, long_at = 2600, 2300
+    genes = [b"G0"] * n_a
+    make_a = lambda path: BamFileByBlocks(path, [rec(i, genes[i], extra=[("zb", "B", ("C", [0] * 3000))] if i == long_at else ()) for i in range(n_a)], 512)
+    f = make_a(str(tmp_path / "layout.bam"))
+    s_long, e_long = int(f.ends[long_at - 1]), int(f.ends[long_at])
+    inside = next(k for k, b in enumerate(f.blocks) if b[2] > s_long and b[3] < e_long)      # a block that holds nothing but bytes of the long record
+    per_a = [1, 256, 257, inside - (f.b0 + 514), 1, 1 << 30]
+    assert per_a[3] > 0
+    plain = [bm.parse_record(r, cfg, dicts) for r in f.recs]
+    shapes = _window_shapes(f, per_a, plain)
+    assert [s[0] for s in shapes[:3]] == [1, 256, 257] and shapes[4][3] == 0 and all(s[4] == 0 for s in shapes)
+    at = 0
+    for (n_blocks, data, segs, n_recs, _), want in zip(shapes, (1, 256, 257)):
+        assert n_recs >= want
+        for i in range(at, at + want):
+            genes[i] = b"G1"
+        at += n_recs
+    f = make_a(str(tmp_path / "a.bam"))
+    # B: records of ~3 KB in blocks of 16 KB
+    fb = BamFileByBlocks(str(tmp_path / "b.bam"), [rec(i, b"G0" if i % 300 else b"G1", seq="ACGT" * 500) for i in range(2800)], 16384)
+    per_b = [256, 256, 1 << 30]
+    seen = {"blocks": set(), "segments": set(), "need": set(), "records": set()}
+    for g, per in ((f, per_a), (fb, per_b)):
+        dec = make_decoder(L, cfg, dicts, pairs, names)
+        try:
+            first = None
+            for mode in ("window", "begin_finish", "pipelined"):
+                if first is not None:
+                    assert L.dropest_bam_decoder_reset(dec, C.byref(c_cfg(cfg))) == 0
+                    set_dicts(L, dec, dicts, pairs, names)
+                res = run_file(L, dec, g, per, mode)
+                rows = check_against_model(g, res, cfg, dicts)
+                shapes = _window_shapes(g, per, rows)
+                # the windows the device saw are the ones counted here, and what it listed is what the model lists
+                assert [(r[0]["blocks"], r[0]["bytes"], r[0]["n_records"], len(r[0]["need"][0])) for r in res] == [(s[0], s[1], s[3], s[4]) for s in shapes], mode
+                if first is None:
+                    first = res
+                    for s in shapes:
+                        seen["blocks"].add(s[0]); seen["segments"].add(s[2]); seen["records"].add(s[3]); seen["need"].add(s[4])
+                else:
+                    assert [r[0] for r in res] == [r[0] for r in first], mode
+                    assert all((a[1][c] == b[1][c]).all() for a, b in zip(first, res) for c in range(4)), mode
+        finally:
+            L.dropest_bam_decoder_destroy(dec)
+    for what in ("blocks", "segments", "need"):
+        assert {1, 256, 257} <= seen[what], (what, sorted(seen[what]))
+    assert 0 in seen["need"] and 0 in seen["records"]
 
 
 CHILD = r"""
