@@ -137,6 +137,7 @@ def lib():
         "dropest_read_corrections": (C.c_int, [vp, u64p, P(vp), P(vp), P(vp)]),
         "dropest_read_corrections_host": (C.c_int, [vp, C.c_uint64, C.c_uint64, vp, vp, vp]),
         "dropest_read_correction_counts": (C.c_int, [vp, vp]),
+        "dropest_cell_barcodes_device": (C.c_int, [vp, u64p, P(vp)]),
         "dropest_add_umi_to_cell": (C.c_int, [vp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, vp, C.c_uint32]),
         "dropest_umi_first_seen": (C.c_int, [vp, u64p, vp]),
         "dropest_set_umi_qualities": (C.c_int, [vp, vp, C.c_uint32, C.c_uint64]),
@@ -274,7 +275,7 @@ EXPORTED_SYMBOLS = [
     "dropest_prefetch_raw_matrix_bytes", "dropest_count_matrix_csc_bytes", "dropest_matrix_bytes_widen", "dropest_matrix_rider_widen", "dropest_set_raw_matrix_prefetch", "dropest_set_matrix_wire", "dropest_set_umi_dictionary", "dropest_debug_refresh", "dropest_push_reads_gather", "dropest_shard_set_umi_qualities", "dropest_shard_set_umi_qualities_var",
     "dropest_debug_poison_scratch", "dropest_debug_trim_pool", "dropest_debug_alloc_ordinal", "dropest_debug_alloc_site",
     "dropest_set_save_umi_merge_targets", "dropest_umi_merge_targets", "dropest_read_corrections", "dropest_read_corrections_host",
-    "dropest_read_correction_counts",
+    "dropest_read_correction_counts", "dropest_cell_barcodes_device",
 ]
 
 
@@ -740,6 +741,12 @@ class Context:
         out = np.zeros(5, np.uint64)
         self._chk(self.L.dropest_read_correction_counts(self.h, out.ctypes.data))
         return out
+
+    def cell_barcodes_device(self):
+        """(n, d_codes): every cell's barcode code by cell id, a raw device pointer valid as long as the read corrections are."""
+        n, p = C.c_uint64(), C.c_void_p()
+        self._chk(self.L.dropest_cell_barcodes_device(self.h, C.byref(n), C.byref(p)))
+        return n.value, p.value
 
     def add_umi_to_cell(self, cell, gene, umi_code, mark, quality=b""):
         q = np.frombuffer(bytes(quality), np.uint8)

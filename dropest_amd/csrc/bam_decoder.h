@@ -148,8 +148,8 @@ struct BamUpload {
 	void reset() { for (int w = 0; w < 2; ++w) { ready[w].store(false, std::memory_order_relaxed); host[w].store(nullptr, std::memory_order_relaxed); } }
 };
 
-// -b (dropest_bam_decoder_set_tagging / _tag_window; k_bamtag.h): the output configuration, the annotation's gene names under -g, the sizes and
-// offsets of the last window's output records and the output itself
+// -b and -F (dropest_bam_decoder_set_tagging / _tag_window, _set_filtering / _filter_window; k_bamtag.h): the output configuration, the
+// annotation's gene names under -g, the sizes and offsets of the last window's output records and the output itself
 struct BamTagging {
 	bool on = false, has_names = false;
 	BamTagCfg cfg{};
@@ -164,7 +164,19 @@ struct BamTagging {
 	bool pending = false;                   // the last emit's flag and time have not been looked at yet (tag_collect, after a wait that is made anyway)
 	double ms = 0;                          // plan + scan + emit by device events, since the decoder was created or reset
 	uint64_t bytes_in = 0, bytes_out = 0;
-	void reset() { on = false; has_names = false; pending = false; len = 0; ms = 0; bytes_in = bytes_out = 0; }      // (the names were the annotation's)
+	// -F (dropest_bam_decoder_set_filtering / _filter_window): the two corrected tags' names, every cell's barcode code (the caller's device array,
+	// or `codes`, a copy of its host array), the side strings of escaped codes, each record's rank among the accepted ones, and a window's
+	// decisions when they come from host arrays (through h_fix, pinned)
+	struct Filtering {
+		bool on = false;
+		uint32_t out_tag[2] = {0, 0}, n_cells = 0, n_side = 0;
+		const uint64_t *cell_barcode = nullptr;
+		DevBuf<uint64_t> codes, umi;
+		DevBuf<uint32_t> side_off, rank, tile_ok, total, cell;
+		DevBuf<uint8_t> side_pool, verdict;
+		PinnedBuf<uint64_t> h_fix;
+	} filt;
+	void reset() { on = false; has_names = false; pending = false; len = 0; ms = 0; bytes_in = bytes_out = 0; filt.on = false; }      // (the names were the annotation's)
 };
 
 // Where the file's windows stand: the record the last chain cut off, the fronts' turns, what the last finished window holds

@@ -1,11 +1,12 @@
-// bam_decoder_tag.h -- -b: the accepted records of the LAST finished window with their tags edited (k_bamtag.h; the state: BamTagging, bam_decoder.h)
+// bam_decoder_tag.h -- -b and -F: the accepted records of the LAST finished window with their tags edited; under -F only those the container's
+// decision writes, with the corrected barcode and UMI behind the other tags (k_bamtag.h; the state: BamTagging, bam_decoder.h)
 #pragma once
 
 extern "C" int dropest_bam_decoder_set_tagging(dropest_bam_decoder *d, const dropest_bam_tag_cfg *cfg) {
 	return bgzf_guarded([&] {
 		if (!d) throw InvalidError("null argument");
 		BamTagging &T = d->tag;
-		T.on = false; T.has_names = false; T.len = 0;
+		T.on = false; T.has_names = false; T.len = 0; T.filt.on = false;      // (-F is configured behind -b: its names are checked against these)
 		if (!cfg) return;
 		static_assert(sizeof(BamTagCfg) == 12 + 12 + 72, "the C struct's first members and the kernels' struct are one layout");
 		for (int k = 0; k < 3; ++k) if (cfg->type_len[k] > 24) throw InvalidError("read-type values longer than 24 characters");
@@ -71,12 +72,19 @@ static BamTagIn tag_in(dropest_bam_decoder *d) {
 }
 
 // each record's output size, the tiles' sums and every record's place; the wait for the one total that sizes the output (in h_tag)
-static void tag_plan(dropest_bam_decoder *d, hipStream_t st, const BamTagIn &in, const BamTagNames &names, uint32_t grid, uint32_t tiles) {
+// (filt: -F -- every record's rank among the accepted ones first, the sizes by the decisions)
+static void tag_plan(dropest_bam_decoder *d, hipStream_t st, const BamTagIn &in, const BamTagNames &names, uint32_t grid, uint32_t tiles, const BamTagFilt *filt) {
 	BamTagging &T = d->tag;
 	const uint32_t n_rec = in.n_rec;
 	HIP_CHECK(hipMemsetAsync(T.flags.p, 0, 4, st));
 	HIP_CHECK(hipEventRecord(T.ev[0], st));
-	hipLaunchKernelGGL(bam_tag_plan_kernel, dim3(grid), dim3(BAMTAG_T), 0, st, in, d->cfg, T.cfg, names, T.size.p, T.flags.p);
+	if (filt) {
+		hipLaunchKernelGGL(bam_tag_rank_tile_kernel, dim3(tiles), dim3(256), 0, st, in.status, n_rec, T.filt.tile_ok.p);
+		hipLaunchKernelGGL(bam_tag_rank_scan_kernel, dim3(1), dim3(1024), 0, st, T.filt.tile_ok.p, tiles, T.filt.total.p);
+		hipLaunchKernelGGL(bam_tag_rank_kernel, dim3(tiles), dim3(256), 0, st, in.status, n_rec, T.filt.tile_ok.p, T.filt.rank.p);
+		hipLaunchKernelGGL(bam_tag_filter_plan_kernel, dim3(grid), dim3(BAMTAG_T), 0, st, in, d->cfg, T.cfg, names, *filt, T.size.p, T.flags.p);
+	} else
+		hipLaunchKernelGGL(bam_tag_plan_kernel, dim3(grid), dim3(BAMTAG_T), 0, st, in, d->cfg, T.cfg, names, T.size.p, T.flags.p);
 	hipLaunchKernelGGL(bam_tag_tile_sum_kernel, dim3(tiles), dim3(256), 0, st, T.size.p, n_rec, T.tile_bytes.p, T.tile_written.p);
 	hipLaunchKernelGGL(bam_tag_tile_scan_kernel, dim3(1), dim3(1024), 0, st, T.tile_bytes.p, T.tile_written.p, tiles, T.flags.p, T.h_tag.p);
 	hipLaunchKernelGGL(bam_tag_offsets_kernel, dim3(tiles), dim3(256), 0, st, T.size.p, n_rec, T.tile_bytes.p, T.off.p);
@@ -89,6 +97,42 @@ static void tag_plan(dropest_bam_decoder *d, hipStream_t st, const BamTagIn &in,
 	T.ms += ms_plan;
 }
 
+// What _tag_window and _filter_window share: plan, the one wait, emit.  filt: -F (its rank pointer and decisions are set by the caller).
+static void tag_run(dropest_bam_decoder *d, const BamTagFilt *filt, const uint8_t **d_out, uint64_t *len, uint64_t *n_written, bool &undecided) {
+	BamTagging &T = d->tag;
+	const uint64_t n_rec = d->at.last_n_rec;
+	hipStream_t st = d->stream;
+	const uint32_t tiles = uint32_t((n_rec + BAMTAG_SCAN_TILE - 1) / BAMTAG_SCAN_TILE);
+	const size_t rc = size_t(n_rec) + size_t(n_rec) / 4;
+	T.size.ensure(rc); T.off.ensure(rc); T.tile_bytes.ensure(tiles + tiles / 4 + 1); T.tile_written.ensure(tiles + tiles / 4 + 1); T.flags.ensure(1);
+	T.h_tag.ensure(4);
+	for (hipEvent_t &e : T.ev) if (!e) HIP_CHECK(hipEventCreate(&e));
+	const BamTagIn in = tag_in(d);
+	const BamTagNames names{d->dict.annotation ? T.name_off.p : nullptr, T.name_pool.p, T.n_names};
+	const uint32_t grid = uint32_t((n_rec + BAMTAG_WAVES - 1) / BAMTAG_WAVES);
+	tag_plan(d, st, in, names, grid, tiles, filt);
+	const uint64_t total = T.h_tag.p[0], written = T.h_tag.p[1];
+	if (T.h_tag.p[2] & BAMTAG_FLAG_RANGE) throw RangeError("the decision of a read that is written names a cell or a side string that does not exist");
+	if (T.h_tag.p[2] & BAMTAG_FLAG_UNDECIDED) {
+		undecided = true;
+		throw UnsupportedError("the annotation query left the gene of some reads to the host: give their genes and marks with dropest_bam_decoder_patch_annotation and tag the window again");
+	}
+	if (!filt && written != d->at.last_n_ok) throw DeviceError("internal: the tagged records and the window's counters disagree");
+	T.bytes_in += d->last().data_len;
+	if (filt && !total) return;                  // (-F: no read of this window is written)
+	T.out.ensure(size_t(total) + size_t(total) / 8 + 64);
+	HIP_CHECK(hipEventRecord(T.ev[2], st));      // (the kernels' time: the host's wait and the allocation between them are not theirs)
+	if (filt) hipLaunchKernelGGL(bam_tag_filter_emit_kernel, dim3(grid), dim3(BAMTAG_T), 0, st, in, d->cfg, T.cfg, names, *filt, T.size.p, T.off.p, T.out.p, total, T.flags.p);
+	else hipLaunchKernelGGL(bam_tag_emit_kernel, dim3(grid), dim3(BAMTAG_T), 0, st, in, d->cfg, T.cfg, names, T.size.p, T.off.p, T.out.p, total, T.flags.p);
+	HIP_CHECK(hipGetLastError());
+	bam_copy(st, 1u, to_host(T.flags.p, reinterpret_cast<uint32_t *>(T.h_tag.p + 3)));
+	HIP_CHECK(hipEventRecord(T.ev[3], st));
+	T.pending = true;                         // its flag (plan and emit disagree: internal) and its time are read after the next wait on the stream
+	T.bytes_out += total;
+	T.len = total;
+	*d_out = T.out.p; *len = total; *n_written = written;
+}
+
 extern "C" int dropest_bam_decoder_tag_window(dropest_bam_decoder *d, const uint8_t **d_out, uint64_t *len, uint64_t *n_written) {
 	bool undecided = false;
 	const int rc = bgzf_guarded([&] {
@@ -98,36 +142,92 @@ extern "C" int dropest_bam_decoder_tag_window(dropest_bam_decoder *d, const uint
 		if (!T.on) throw InvalidError("tagging is not configured for this decoder (dropest_bam_decoder_set_tagging)");
 		if (d->dict.annotation && !T.has_names) throw InvalidError("with an annotation the tagging configuration must bring its gene names");
 		T.len = 0;
+		if (!d->at.last_n_rec) return;
+		HIP_CHECK(hipSetDevice(d->device));
+		bam_ready(d);
+		tag_run(d, nullptr, d_out, len, n_written, undecided);
+	});
+	return rc && undecided ? 2 : rc;
+}
+
+// ---- -F ----------------------------------------------------------------------------------------------------------------------------------------
+extern "C" int dropest_bam_decoder_set_filtering(dropest_bam_decoder *d, const dropest_bam_filter_cfg *cfg) {
+	return bgzf_guarded([&] {
+		if (!d) throw InvalidError("null argument");
+		BamTagging &T = d->tag;
+		BamTagging::Filtering &F = T.filt;
+		F.on = false; T.len = 0;
+		if (!cfg) return;
+		if (!T.on) throw InvalidError("filtering needs the tagging configuration first (dropest_bam_decoder_set_tagging): the other six tags come from there");
+		if ((cfg->n_cells && !cfg->cell_barcode) || (cfg->n_side && (!cfg->side_off || !cfg->side_pool))) throw InvalidError("null argument");
+		const uint32_t mine[2] = {cfg->out_tag[0], cfg->out_tag[1]};
+		bool shared = mine[0] && mine[0] == mine[1];
+		for (int k = 0; k < 2; ++k) {
+			for (int j = 0; j < 5; ++j) shared |= mine[k] && mine[k] == T.cfg.out_tag[j];
+			shared |= mine[k] && mine[k] == T.cfg.type_tag;
+		}
+		if (shared) throw InvalidError("two output tags share a name: the corrected barcode and UMI tags need names of their own");
+		const uint32_t n_side = cfg->n_side, side_bytes = n_side ? cfg->side_off[n_side] : 0u;
+		for (uint32_t k = 0; k < n_side; ++k) if (cfg->side_off[k] > cfg->side_off[k + 1]) throw InvalidError("the side strings' offsets must not decrease");
+		HIP_CHECK(hipSetDevice(d->device));
+		bam_ready(d);
+		HIP_CHECK(hipStreamSynchronize(d->stream));
+		const size_t code_bytes = cfg->on_device ? 0 : size_t(cfg->n_cells) * 8;
+		d->dict.h_dict.ensure(code_bytes + (size_t(n_side) + 1) * 4 + size_t(side_bytes) + 256);
+		size_t at = 0;
+		F.cell_barcode = cfg->cell_barcode;
+		if (!cfg->on_device) {
+			F.codes.ensure(size_t(cfg->n_cells) + 1);
+			bam_to_device(d, F.codes.p, cfg->cell_barcode, code_bytes, at);
+			F.cell_barcode = F.codes.p;
+		}
+		F.side_off.ensure(size_t(n_side) + 1); F.side_pool.ensure(size_t(side_bytes) + 16);
+		if (n_side) bam_to_device(d, F.side_off.p, cfg->side_off, (size_t(n_side) + 1) * 4, at);
+		if (side_bytes) bam_to_device(d, F.side_pool.p, cfg->side_pool, side_bytes, at);
+		HIP_CHECK(hipStreamSynchronize(d->stream));
+		F.out_tag[0] = mine[0]; F.out_tag[1] = mine[1]; F.n_cells = cfg->n_cells; F.n_side = n_side;
+		F.on = true;
+	});
+}
+
+extern "C" int dropest_bam_decoder_filter_window(dropest_bam_decoder *d, const uint8_t *verdict, const uint32_t *cell, const uint64_t *umi, uint64_t n, int on_device,
+                                                 const uint8_t **d_out, uint64_t *len, uint64_t *n_written) {
+	bool undecided = false;
+	const int rc = bgzf_guarded([&] {
+		if (!d || !d_out || !len || !n_written || (n && (!verdict || !cell || !umi))) throw InvalidError("null argument");
+		*d_out = nullptr; *len = 0; *n_written = 0;
+		BamTagging &T = d->tag;
+		BamTagging::Filtering &F = T.filt;
+		if (!T.on) throw InvalidError("tagging is not configured for this decoder (dropest_bam_decoder_set_tagging)");
+		if (!F.on) throw InvalidError("filtering is not configured for this decoder (dropest_bam_decoder_set_filtering)");
+		if (d->dict.annotation && !T.has_names) throw InvalidError("with an annotation the tagging configuration must bring its gene names");
+		T.len = 0;
+		if (n != d->at.last_n_ok) throw InvalidError(std::to_string(n) + " decisions for a window of " + std::to_string(d->at.last_n_ok) + " accepted records");
 		const uint64_t n_rec = d->at.last_n_rec;
 		if (!n_rec) return;
 		HIP_CHECK(hipSetDevice(d->device));
 		bam_ready(d);
-		hipStream_t st = d->stream;
 		const uint32_t tiles = uint32_t((n_rec + BAMTAG_SCAN_TILE - 1) / BAMTAG_SCAN_TILE);
-		const size_t rc = size_t(n_rec) + size_t(n_rec) / 4;
-		T.size.ensure(rc); T.off.ensure(rc); T.tile_bytes.ensure(tiles + tiles / 4 + 1); T.tile_written.ensure(tiles + tiles / 4 + 1); T.flags.ensure(1);
-		T.h_tag.ensure(4);
-		for (hipEvent_t &e : T.ev) if (!e) HIP_CHECK(hipEventCreate(&e));
-		const BamTagIn in = tag_in(d);
-		const BamTagNames names{d->dict.annotation ? T.name_off.p : nullptr, T.name_pool.p, T.n_names};
-		const uint32_t grid = uint32_t((n_rec + BAMTAG_WAVES - 1) / BAMTAG_WAVES);
-		tag_plan(d, st, in, names, grid, tiles);
-		const uint64_t total = T.h_tag.p[0], written = T.h_tag.p[1];
-		if (T.h_tag.p[2] & BAMTAG_FLAG_UNDECIDED) {
-			undecided = true;
-			throw UnsupportedError("the annotation query left the gene of some reads to the host: give their genes and marks with dropest_bam_decoder_patch_annotation and tag the window again");
+		F.rank.ensure(size_t(n_rec) + size_t(n_rec) / 4); F.tile_ok.ensure(tiles + tiles / 4 + 1); F.total.ensure(1);
+		BamTagFilt f{};
+		f.rank = F.rank.p; f.verdict = verdict; f.cell = cell; f.umi = umi; f.n = uint32_t(n);
+		if (!on_device && n) {      // host arrays: through pinned staging, moved by a kernel's own loads (from_host)
+			const size_t m = size_t(n);
+			F.umi.ensure(m + m / 4); F.cell.ensure(m + m / 4); F.verdict.ensure(m + m / 4);
+			HIP_CHECK(hipStreamSynchronize(d->stream));      // (a call before this one that failed half-way may still be reading the staging)
+			F.h_fix.ensure(m + m / 2 + m / 8 + 8);      // words of 8 bytes: UMI | cell | verdict
+			size_t at = 0;
+			const char *const what = "the decisions' staging";
+			const uint64_t *const q_umi = pinned_put(F.h_fix, at, umi, m, what);
+			const uint32_t *const q_cell = pinned_put(F.h_fix, at, cell, m, what);
+			const uint8_t *const q_verdict = pinned_put(F.h_fix, at, verdict, m, what);
+			bam_copy(d->stream, uint32_t(m), from_host(q_umi, F.umi.p), from_host(q_cell, F.cell.p), from_host(q_verdict, F.verdict.p));
+			f.verdict = F.verdict.p; f.cell = F.cell.p; f.umi = F.umi.p;      // (tag_run waits for the stream before it returns: the staging is free again)
 		}
-		if (written != d->at.last_n_ok) throw DeviceError("internal: the tagged records and the window's counters disagree");
-		T.out.ensure(size_t(total) + size_t(total) / 8 + 64);
-		HIP_CHECK(hipEventRecord(T.ev[2], st));      // (the kernels' time: the host's wait and the allocation between them are not theirs)
-		hipLaunchKernelGGL(bam_tag_emit_kernel, dim3(grid), dim3(BAMTAG_T), 0, st, in, d->cfg, T.cfg, names, T.size.p, T.off.p, T.out.p, total, T.flags.p);
-		HIP_CHECK(hipGetLastError());
-		bam_copy(st, 1u, to_host(T.flags.p, reinterpret_cast<uint32_t *>(T.h_tag.p + 3)));
-		HIP_CHECK(hipEventRecord(T.ev[3], st));
-		T.pending = true;                         // its flag (plan and emit disagree: internal) and its time are read after the next wait on the stream
-		T.bytes_in += d->last().data_len; T.bytes_out += total;
-		T.len = total;
-		*d_out = T.out.p; *len = total; *n_written = written;
+		f.cell_barcode = F.cell_barcode; f.n_cells = F.n_cells;
+		f.side_off = F.side_off.p; f.side_pool = F.side_pool.p; f.n_side = F.n_side;
+		f.out_tag[0] = F.out_tag[0]; f.out_tag[1] = F.out_tag[1];
+		tag_run(d, &f, d_out, len, n_written, undecided);
 	});
 	return rc && undecided ? 2 : rc;
 }

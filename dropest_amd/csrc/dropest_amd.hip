@@ -2427,6 +2427,16 @@ dropest_status dropest_read_correction_counts(dropest_ctx *ctx, uint64_t out[5])
 	});
 }
 
+dropest_status dropest_cell_barcodes_device(dropest_ctx *ctx, uint64_t *n, const uint64_t **d_codes) {
+	return guarded([&] {
+		if (!ctx || !n || !d_codes) throw InvalidError("null argument");
+		HIP_CHECK(hipSetDevice(ctx->cfg.device));
+		ctx->build_read_corrections();      // (refuses what the corrections refuse; the cells' barcodes are the pass's own array: nothing is copied)
+		*n = ctx->n_cells;
+		*d_codes = reinterpret_cast<const uint64_t *>(ctx->cell_cb.p);
+	});
+}
+
 dropest_status dropest_set_umi_qualities(dropest_ctx *ctx, const uint8_t *qualities, uint32_t quality_length, uint64_t n_reads) {
 	return guarded([&] {
 		if (!ctx) throw InvalidError("null context");

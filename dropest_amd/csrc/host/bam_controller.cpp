@@ -238,6 +238,7 @@ void BamController::parse_bam_files(const std::vector<std::string> &bam_files, C
 void BamController::parse_bam_files(const std::vector<std::string> &bam_files, bool print_result_bams, CellsDataContainer &container) {
 	const BamSwitches sw = BamSwitches::from_environment();
 	_tagged.clear();
+	_saved_per_file.clear();
 	if (print_result_bams) {      // what the device path refuses, said before any file is read: the host reader does not write BAM
 		const char *why = nullptr;
 		if (_params_from_files) why = "read-parameter files (-r) are served by the host reader";
@@ -251,6 +252,7 @@ void BamController::parse_bam_files(const std::vector<std::string> &bam_files, b
 	join_release_thread();
 	for (auto const &bam_name : bam_files) {
 		FileIngest file(sw, bam_name, bam_files.size(), container, _counters, _tags, _filled_bam, _params_from_files, _gene_in_chromosome_name, _min_barcode_phred, _genes, nthreads);
+		struct NoteSaved { std::vector<size_t> &per_file; const Counters &c; size_t before; ~NoteSaved() { per_file.push_back(c.saved - before); } } note{_saved_per_file, _counters, _counters.saved};
 		if (print_result_bams) { _tagged.emplace_back(); file.tagged = &_tagged.back(); }
 		if (print_result_bams || _device_decode || sw.device) {
 			const auto t_df = clk::now();
@@ -263,6 +265,45 @@ void BamController::parse_bam_files(const std::vector<std::string> &bam_files, b
 		read_file_on_host(file, &bam_name == &bam_files.front());
 	}
 	// the device decoders' memory goes back before the container sorts (the cache was never released)
+	if (!sw.keep_decoders) release_decoders_in_background();
+}
+
+// -F: the second pass over the files (bam_ingest.h); every file through the device path in its filtered mode (bam_device.cpp)
+void BamController::write_filtered_bam_files(const std::vector<std::string> &bam_files, CellsDataContainer &container) {
+	const BamSwitches sw = BamSwitches::from_environment();
+	_filtered = FilteredFile();
+	const char *why = nullptr;
+	if (_params_from_files) why = "read-parameter files (-r) are served by the host reader";
+	else if (_gene_in_chromosome_name) why = "gene = chromosome name is resolved by the host reader";
+	else if (_tags.intronic_read_value.size() > 24 || _tags.intergenic_read_value.size() > 24 || _tags.exonic_read_value.size() > 24) why = "a read-type value is longer than 24 bytes";
+	if (why) throw std::runtime_error(std::string("Filtered BAM output (-F) is written on the device BAM path only, which this configuration cannot take: ") + why);
+	if (bam_files.empty()) return;
+	join_release_thread();
+	FilteredPass *pass = filtered_pass_open(sw, container, _filtered);
+	Counters second_pass;      // (the reads were counted when the container was filled)
+	try {
+		// did this controller fill the container?  Then file k brings what it brought then (a count guard per file: it sees files in another order)
+		size_t remembered = 0;
+		for (size_t n : _saved_per_file) remembered += n;
+		const bool per_file = !_saved_per_file.empty() && remembered == filtered_pass_total(pass);
+		for (auto const &bam_name : bam_files) {
+			const uint64_t before = filtered_pass_reads(pass);
+			const size_t k = size_t(&bam_name - &bam_files.front());
+			FileIngest file(sw, bam_name, bam_files.size(), container, second_pass, _tags, _filled_bam, _params_from_files, _gene_in_chromosome_name, _min_barcode_phred, _genes, 1);
+			file.filtered = pass;
+			if (!read_file_on_device(file))
+				throw std::runtime_error("Filtered BAM output (-F) is written on the device BAM path only, which cannot take this file: " + (file.refusal.empty() ? std::string("unknown reason") : file.refusal) + ": " + bam_name);
+			const uint64_t brought = filtered_pass_reads(pass) - before;
+			if (per_file && (k >= _saved_per_file.size() || brought != _saved_per_file[k]))
+				filtered_pass_other_files(pass, bam_name + " brings " + std::to_string(brought) + " accepted reads, file " + std::to_string(k + 1) + " of the call that filled the container brought " +
+				                                (k < _saved_per_file.size() ? std::to_string(_saved_per_file[k]) : std::string("none")));
+		}
+	} catch (...) {
+		filtered_pass_close(pass, false);
+		if (!sw.keep_decoders) release_decoders_in_background();
+		throw;
+	}
+	filtered_pass_close(pass, true);
 	if (!sw.keep_decoders) release_decoders_in_background();
 }
 

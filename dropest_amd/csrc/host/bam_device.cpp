@@ -12,6 +12,10 @@
 // Tagged BAM output (-b: parse_bam_files(files, true, container)) is made here and only here: every window's accepted records are edited on the device
 // (csrc/k_bamtag.h) before the window goes into the container, compressed there and written to `<input stem>.tagged.bam` (open_tagged, tag_window,
 // close_tagged); a file this path refuses is then an error that names the reason (FileIngest::refusal), not a file for the host reader.
+// Filtered BAM output (-F: BamController::write_filtered_bam_files) is this path's second mode (FileIngest::filtered): the files are decoded again,
+// nothing goes into the container, every window's accepted records are edited by the tag kernels' filtered mode under the container's per-read
+// decisions (dropest_bam_decoder_filter_window; the decisions stay on the device) and ONE compressor stream writes the one output of the call
+// (FilteredPass, open_filtered, filter_window, close_filtered).
 // A sharded container is fed the same way: ONE decoder, on the GPU of the shard the file's first read goes to and on that shard's stream, for the
 // whole file (the record cut off at a window's end waits inside it); the container cuts every window at its quota boundaries and appends the
 // pieces to the shards' resident reads, device to device.
@@ -19,12 +23,14 @@
 #include "../../../include/dropest_bgzf.h"
 #include "../../../include/dropest_annotation.h"
 #include "../../../include/dropest_deflate.h"
+#include "../../../include/dropest_amd.h"
 
 #include <fcntl.h>
 #include <sys/mman.h>
 #include <sys/stat.h>
 
 #include <atomic>
+#include <memory>
 
 namespace Estimation {
 namespace BamProcessing {
@@ -60,6 +66,77 @@ void BamController::release_device_decoders() {
 	std::lock_guard<std::mutex> lk(decoder_cache_mutex());
 	for (auto &kv : decoder_cache()) dropest_bam_decoder_destroy(kv.second);
 	decoder_cache().clear();
+}
+
+// -F: what the files of one write_filtered_bam_files call share (bam_parse.h)
+struct FilteredPass {
+	const BamSwitches &sw;
+	CellsDataContainer &container;
+	BamController::FilteredFile &report;
+	const uint8_t *d_verdict = nullptr; const uint32_t *d_cell = nullptr; const uint64_t *d_umi = nullptr;      // dropest_read_corrections: device arrays of the context
+	const uint64_t *d_cell_codes = nullptr;                                                                     // dropest_cell_barcodes_device
+	uint64_t n_reads = 0, n_cells = 0, at = 0, written = 0;      // at: accepted records of the files so far = the next window's first decision
+	uint64_t counts[5] = {0, 0, 0, 0, 0};
+	std::vector<uint32_t> side_off; std::vector<uint8_t> side_pool;      // the container's side strings as the decoder takes them
+	std::string name;
+	std::FILE *f = nullptr;
+	dropest_deflate_stream *z = nullptr;
+	size_t windows = 0;
+	double decode_ms = 0, tag_ms = 0;
+	FilteredPass(const BamSwitches &sw, CellsDataContainer &container, BamController::FilteredFile &report) : sw(sw), container(container), report(report) {}
+	~FilteredPass() { if (z) dropest_deflate_stream_destroy(z); if (f) std::fclose(f); }
+	static int write(const uint8_t *bytes, uint64_t len, void *user) { return std::fwrite(bytes, 1, size_t(len), static_cast<FilteredPass *>(user)->f) == size_t(len) ? 0 : 1; }
+	[[noreturn]] void other_files(const std::string &what) const {
+		throw std::runtime_error("Filtered BAM output (-F): " + what + ": these are not the files the container was filled from (the same files, in the same order)");
+	}
+};
+
+FilteredPass *filtered_pass_open(const BamSwitches &sw, CellsDataContainer &container, BamController::FilteredFile &report) {
+	// (a sharded or split container has no one context that holds every read: a shard's context says so in the read corrections' own words)
+	dropest_ctx *const ctx = container.sharded() ? dropest_shard_ctx(container.shard0()) : container.handle();
+	std::unique_ptr<FilteredPass> p(new FilteredPass(sw, container, report));
+	if (!ctx || dropest_read_corrections(ctx, &p->n_reads, &p->d_verdict, &p->d_cell, &p->d_umi) != DROPEST_OK ||
+	    dropest_cell_barcodes_device(ctx, &p->n_cells, &p->d_cell_codes) != DROPEST_OK || dropest_read_correction_counts(ctx, p->counts) != DROPEST_OK)
+		throw std::runtime_error(std::string("Filtered BAM output (-F): ") + (ctx ? dropest_last_error() : "the container holds no reads"));
+	if (p->n_cells > 0xFFFFFFFFull) throw std::runtime_error("Filtered BAM output (-F): more than 2^32 cells");
+	const std::vector<std::string> &side = container.side_strings();
+	p->side_off.push_back(0);
+	for (const std::string &s : side) { p->side_pool.insert(p->side_pool.end(), s.begin(), s.end()); p->side_off.push_back(uint32_t(p->side_pool.size())); }
+	if (p->side_pool.size() > 0xFFFFFFF0ull) throw std::runtime_error("Filtered BAM output (-F): the side strings pass 4 GB");
+	p->side_pool.push_back(0);
+	return p.release();
+}
+
+uint64_t filtered_pass_reads(const FilteredPass *pass) { return pass->at; }
+uint64_t filtered_pass_total(const FilteredPass *pass) { return pass->n_reads; }
+void filtered_pass_other_files(const FilteredPass *pass, const std::string &what) { pass->other_files(what); }
+
+void filtered_pass_close(FilteredPass *pass, bool ok) {
+	std::unique_ptr<FilteredPass> p(pass);
+	BamController::FilteredFile &r = p->report;
+	r = BamController::FilteredFile();
+	auto drop = [&] {      // no half-written file, no half-written claim
+		if (p->z) { dropest_deflate_stream_destroy(p->z); p->z = nullptr; }
+		if (p->f) { std::fclose(p->f); p->f = nullptr; std::remove(p->name.c_str()); }
+	};
+	if (!ok) { drop(); return; }
+	try {
+		if (p->at != p->n_reads) p->other_files("the files hold " + std::to_string(p->at) + " accepted reads, the container " + std::to_string(p->n_reads));
+		if (p->written != p->counts[0]) throw std::runtime_error("internal: " + std::to_string(p->written) + " reads were written to the filtered BAM file, the container's decisions write " + std::to_string(p->counts[0]));
+		if (!p->z) throw std::runtime_error("internal: no filtered BAM file was opened");
+		if (dropest_deflate_stream_finish(p->z, DROPEST_DEFLATE_EOF)) throw std::runtime_error(std::string(dropest_deflate_last_error()) + ": " + p->name);
+		uint64_t in = 0, out = 0, batches = 0;
+		double deflate_ms = 0;
+		(void)dropest_deflate_stream_stats(p->z, &deflate_ms, &in, &out, &batches);
+		dropest_deflate_stream_destroy(p->z); p->z = nullptr;
+		const bool closed = std::fclose(p->f) == 0;
+		p->f = nullptr;
+		if (!closed) { std::remove(p->name.c_str()); throw std::runtime_error("Can't write filtered BAM file: " + p->name); }
+		r.name = p->name; r.windows = p->windows; r.total_reads = size_t(p->at); r.written = size_t(p->written);
+		r.wrong_genes = size_t(p->counts[3]); r.wrong_umis = size_t(p->counts[4]);
+		r.inflated_bytes = size_t(in); r.compressed_bytes = size_t(out); r.batches = size_t(batches);
+		r.decode_ms = p->decode_ms; r.tag_ms = p->tag_ms; r.deflate_ms = deflate_ms;
+	} catch (...) { drop(); throw; }
 }
 
 namespace {
@@ -183,7 +260,11 @@ class DeviceFileReader {
 		static int write(const uint8_t *bytes, uint64_t len, void *user) { return std::fwrite(bytes, 1, size_t(len), static_cast<TaggedOut *>(user)->f) == size_t(len) ? 0 : 1; }
 	} tagged;
 	std::vector<uint8_t> header_bytes;      // magic, text, references: the tagged file begins with them, byte for byte
+	void tagging_to_decoder();
 	void open_tagged();
+	void open_filtered();
+	void filter_window(const dropest_bam_window &w);
+	void close_filtered();
 	void tag_window(const dropest_bam_window &w);
 	void patch_host_decided(const dropest_bam_window &w);
 	std::unordered_map<std::string, uint32_t> ann_gene_index;      // -g: the annotation's gene names -> its gene indices
@@ -268,8 +349,8 @@ void DeviceFileReader::read_header() {
 		refs.emplace_back(reinterpret_cast<const char *>(hdr.data() + h + 4), ln ? ln - 1 : 0);
 		h += 4 + ln + 4;
 	}
-	container.set_reference_names(refs);
-	if (file.tagged) header_bytes.assign(hdr.begin(), hdr.begin() + h);
+	if (!file.filtered) container.set_reference_names(refs);      // (-F changes nothing in the container)
+	if (file.tagged || (file.filtered && !file.filtered->f)) header_bytes.assign(hdr.begin(), hdr.begin() + h);
 	c0 = at; u0 = 0;                                // the header ends with a block: the records open the next one
 	for (size_t k = starts.size(); k-- > 0;)
 		if (starts[k].second <= h && h < (k + 1 < starts.size() ? starts[k + 1].second : hdr.size())) { c0 = starts[k].first; u0 = uint32_t(h - starts[k].second); break; }
@@ -325,10 +406,9 @@ bool DeviceFileReader::annotation_to_device() {
 	return true;
 }
 
-// (c) -b: the output tag names and read-type values (BamTags.cpp:7-24; an out-value is the configured in-value, else EXONIC / INTRONIC /
-// INTERGENIC), under -g the annotation's gene names; `<input stem>.tagged.bam` in the current directory (BamProcessor::get_result_bam_name,
-// BamProcessorAbstract::update_bam strips the directory); the header's bytes go in first
-void DeviceFileReader::open_tagged() {
+// (c) -b and -F: the output tag names and read-type values (BamTags.cpp:7-24; an out-value is the configured in-value, else EXONIC / INTRONIC /
+// INTERGENIC), under -g the annotation's gene names
+void DeviceFileReader::tagging_to_decoder() {
 	const BamTags &t = parser.tags;
 	dropest_bam_tag_cfg tc{};
 	const std::string *names[5] = {&t.gene, &t.cell_barcode_raw, &t.umi_raw, &t.cell_barcode_quality, &t.umi_quality};
@@ -345,6 +425,12 @@ void DeviceFileReader::open_tagged() {
 		tc.gene_name_off = off.data(); tc.gene_name_pool = pool.data(); tc.n_gene_names = uint32_t(flat.gene_names.size());
 	}
 	if (dropest_bam_decoder_set_tagging(dec, &tc)) fail();
+}
+
+// (c) -b: `<input stem>.tagged.bam` in the current directory (BamProcessor::get_result_bam_name, BamProcessorAbstract::update_bam strips the
+// directory); the header's bytes go in first
+void DeviceFileReader::open_tagged() {
+	tagging_to_decoder();
 	std::string name = file.bam_name.substr(0, file.bam_name.find_last_of('.')) + ".tagged.bam";
 	const size_t slash = name.find_last_of("\\/");
 	if (slash != std::string::npos) name = name.substr(slash + 1);
@@ -354,6 +440,53 @@ void DeviceFileReader::open_tagged() {
 	if (dropest_deflate_stream_create(target.device, dropest_bam_decoder_stream(dec), sw.tagged_batch, TaggedOut::write, &tagged, &tagged.z) ||
 	    dropest_deflate_stream_put(tagged.z, header_bytes.data(), header_bytes.size(), 0))
 		throw std::runtime_error(std::string(dropest_deflate_last_error()) + ": " + name);
+}
+
+// (c) -F: the six tags of -b, then the two corrected ones, their values' tables (every cell's barcode code: the context's device array; the
+// container's side strings) to this file's decoder.  The FIRST file of the call opens the one output, `<its stem>.filtered.bam` in the current
+// directory, with its header's bytes (FilteringBamProcessor::update_bam, :103-110: _is_bam_open); the compressor runs on the container's stream,
+// which every file's decoder is lent.
+void DeviceFileReader::open_filtered() {
+	FilteredPass &P = *file.filtered;
+	tagging_to_decoder();
+	dropest_bam_filter_cfg fc{};
+	fc.out_tag[0] = RecordParser::tag16(parser.tags.cell_barcode); fc.out_tag[1] = RecordParser::tag16(parser.tags.umi);
+	fc.on_device = 1; fc.cell_barcode = P.d_cell_codes; fc.n_cells = uint32_t(P.n_cells);
+	fc.n_side = uint32_t(P.side_off.size() - 1); fc.side_off = P.side_off.data(); fc.side_pool = P.side_pool.data();
+	if (dropest_bam_decoder_set_filtering(dec, &fc)) fail();
+	if (P.f) return;
+	std::string name = file.bam_name.substr(0, file.bam_name.find_last_of('.')) + ".filtered.bam";
+	const size_t slash = name.find_last_of("\\/");
+	if (slash != std::string::npos) name = name.substr(slash + 1);
+	P.name = name;
+	P.f = std::fopen(name.c_str(), "wb");
+	if (!P.f) throw std::runtime_error("Can't write filtered BAM file: " + name);
+	if (dropest_deflate_stream_create(target.device, dropest_bam_decoder_stream(dec), sw.tagged_batch, FilteredPass::write, &P, &P.z) ||
+	    dropest_deflate_stream_put(P.z, header_bytes.data(), header_bytes.size(), 0))
+		throw std::runtime_error(std::string(dropest_deflate_last_error()) + ": " + name);
+}
+
+// (g) -F: the window the decoder holds under the decisions of its accepted records -- entries [at, at + n_accepted) of the container's, where they are
+void DeviceFileReader::filter_window(const dropest_bam_window &w) {
+	FilteredPass &P = *file.filtered;
+	const uint64_t n = w.n_accepted;
+	if (n > P.n_reads - P.at) P.other_files("a window of " + file.bam_name + " brings the accepted reads to " + std::to_string(P.at + n) + ", the container holds " + std::to_string(P.n_reads));
+	const uint8_t *d_out = nullptr;
+	uint64_t len = 0, written = 0;
+	int rc = dropest_bam_decoder_filter_window(dec, P.d_verdict + P.at, P.d_cell + P.at, P.d_umi + P.at, n, 1, &d_out, &len, &written);
+	if (rc == 2) { patch_host_decided(w); rc = dropest_bam_decoder_filter_window(dec, P.d_verdict + P.at, P.d_cell + P.at, P.d_umi + P.at, n, 1, &d_out, &len, &written); }
+	if (rc) fail();
+	if (len && dropest_deflate_stream_put(P.z, d_out, len, 1)) throw std::runtime_error(std::string(dropest_deflate_last_error()) + ": " + P.name);
+	P.at += n; P.written += written; ++P.windows;
+	P.decode_ms += w.ms_copy + w.ms_inflate + w.ms_boundaries + w.ms_parse;
+}
+
+// (h) -F: this file's share of the tag kernels' time; the decoder may be kept for a call that writes nothing
+void DeviceFileReader::close_filtered() {
+	double ms = 0;
+	(void)dropest_bam_decoder_tag_stats(dec, &ms, nullptr, nullptr);
+	file.filtered->tag_ms += ms;
+	(void)dropest_bam_decoder_set_tagging(dec, nullptr);
 }
 
 // (g) -b: the window the decoder holds, tagged, to the compressor (on the decoder's stream: the bytes are copied before the next window overwrites them)
@@ -526,6 +659,7 @@ void DeviceFileReader::dictionaries_to_device() {
 	const auto t_phase = clk::now();
 	if (dict_dirty) {
 		container.dictionary_snapshot(dict_hash, dict_id, dict_chr);
+		if (file.filtered) dict_chr.assign(file.refs.size(), 0);      // (-F looks at no chromosome: every reference counts as met, so that none makes a need record)
 		if (dropest_bam_decoder_set_dictionaries(dec, dict_hash.data(), dict_id.data(), uint32_t(dict_hash.size()), dict_chr.data(), uint32_t(dict_chr.size()))) fail();
 		{   // ... and the genes' names: a hash the device finds is confirmed byte by byte (two names with one FNV-1a value must not share an index)
 			const auto &names = container.gene_indexer().values();
@@ -595,6 +729,7 @@ void DeviceFileReader::resolve_new(const dropest_bam_window &w) {
 // (g) one decoded window into the container and the counters
 void DeviceFileReader::take_window(const dropest_bam_window &w, size_t used, clk::time_point t_call) {
 	ms_window_calls += since(t_call);
+	if (file.filtered) { first = false; ++n_windows; filter_window(w); return; }      // the second pass: nothing goes into the container
 	if (file.tagged) tag_window(w);      // first thing: whichever way the window then goes into the container, its accepted records are written
 	if (first) {
 		est_reads = size_t(double(w.n_records) * double(map.n - c0) / double(std::max<size_t>(used, 1)) * double(file.n_files) * 1.05);
@@ -694,6 +829,7 @@ bool DeviceFileReader::read() {
 	ms_create = since(t_enter) - ms_header;
 	if (!annotation_to_device()) { file.refusal = "the gene annotation cannot be held on the device"; return false; }
 	if (file.tagged) open_tagged();
+	if (file.filtered) open_filtered();
 	t_file = clk::now();
 	// (1 MB first: the file's genes and chromosomes are mostly met there, and every one of them is a record the host parses -- a first window of
 	// 4 / 8 / 16 MB: 65 -> 76 / 79 / 87 ms on the 3.2 x file; then x 8: 1, 8, 64 MB ... measured against x 4 and x 16 with the round's final decoder:
@@ -706,6 +842,7 @@ bool DeviceFileReader::read() {
 	read_next();
 	if (sw.pipeline) windows_pipelined(); else windows_one_by_one();
 	if (file.tagged) close_tagged();
+	if (file.filtered) close_filtered();
 	sw.trace("[bam] device path: %zu windows, %.1f ms behind the header; copy in %.1f ms, inflate %.1f ms (%zu blocks left to the host), record chain %.1f ms (%zu guesses "
 	         "repaired), fields + dense columns %.1f ms; host: dictionaries to the device %.1f ms, %zu records with something new %.1f ms, container %.1f ms\n",
 	         n_windows, since(t_file), dev_ms[0], dev_ms[1], refused, dev_ms[2], repaired, dev_ms[3], host_ms[0], n_needs, host_ms[1], host_ms[2]);
@@ -723,7 +860,7 @@ bool read_file_on_device(FileIngest &file) {
 	if (parser.params_from_files) { file.refusal = "read-parameter files (-r) are served by the host reader"; return false; }
 	if (parser.gene_in_chromosome_name) { file.refusal = "gene = chromosome name is resolved by the host reader"; return false; }
 	// (-b stays here whatever the container takes: a window it cannot take in bulk goes through records_through_host, record by record if need be)
-	if (!file.tagged && !file.container.bulk_ingest_possible_at_all(true)) { file.refusal = "the container no longer takes reads in bulk"; return false; }
+	if (!file.tagged && !file.filtered && !file.container.bulk_ingest_possible_at_all(true)) { file.refusal = "the container no longer takes reads in bulk"; return false; }
 	const CellsDataContainer::IngestTarget target = file.container.next_read_target();
 	const auto t_enter = clk::now();
 	if (parser.tags.intronic_read_value.size() > 24 || parser.tags.intergenic_read_value.size() > 24) { file.refusal = "a read-type value is longer than 24 bytes"; return false; }

@@ -9,7 +9,9 @@
 //   ReadParamsParser::get_gene_from_reference (-g: gene annotation from a GTF / BED file, gene_annotation.h)
 //   ReadMapParamsParser::get_read_params (-r: droptag's read-parameter files "name cb umi cb_quality umi_quality", gzip;
 //     ReadMapParamsParser.cpp:22-48, :50-108; every name serves once)
-// Tagged BAM output (-b) is written on the device path only (parse_bam_files(files, true, container)).  Not built: filtered BAM output (-F).
+//   FilteringBamProcessor::write_alignment / update_bam (-F: FilteringBamProcessor.cpp:61-110) through BamController::write_filtered_bam_files
+// Tagged BAM output (-b: parse_bam_files(files, true, container)) and filtered BAM output (-F: write_filtered_bam_files) are written on the device
+// path only.
 //
 // The container format: BGZF (gzip members with a 'BC' extra field, SAMv1 §4.1) holding the BAM stream (§4.2).
 // Blocks are inflated by a pool of host threads, records are parsed in stream order by the caller's thread (the
@@ -88,6 +90,14 @@ public:
 		double tag_ms = 0, deflate_ms = 0;              // the tag kernels (plan, scan, emit) and the compressor's launches, by device events
 		size_t tag_bytes_in = 0, tag_bytes_out = 0;     // inflated bytes of the windows the tag kernels looked at, bytes they wrote
 	};
+	// -F: the one `<first input's stem>.filtered.bam` that write_filtered_bam_files wrote
+	struct FilteredFile {
+		std::string name;
+		size_t windows = 0, total_reads = 0, written = 0;   // windows decoded; accepted alignments that reached write_alignment; those it wrote
+		size_t wrong_genes = 0, wrong_umis = 0;              // FilteringBamProcessor::trace_state's numbers (dropest_read_correction_counts [3], [4])
+		size_t inflated_bytes = 0, compressed_bytes = 0, batches = 0;
+		double decode_ms = 0, tag_ms = 0, deflate_ms = 0;    // the decoder's kernels and copies, the tag kernels, the compressor's launches: by device events
+	};
 private:
 	BamTags _tags;
 	struct ReadParams { std::string cb, umi, umi_quality; bool pass_quality; };
@@ -103,6 +113,8 @@ private:
 	bool _device_decode = false;
 	Counters _counters;
 	std::vector<TaggedFile> _tagged;
+	FilteredFile _filtered;
+	std::vector<size_t> _saved_per_file;             // accepted reads of every file of the last parse_bam_files call, for write_filtered_bam_files' guard
 	Tools::GeneAnnotation::RefGenesContainer _genes;   // -g: empty unless a GTF / BED file was given
 public:
 	// gtf_path: GTF / BED annotation (-g), "" = genes come from the BAM's gene tag; read_param_filenames must be empty (not built)
@@ -118,6 +130,20 @@ public:
 	// bytes, no GPU -- throws std::runtime_error naming the reason: the host reader does not write BAM.  false: the call above.
 	void parse_bam_files(const std::vector<std::string> &bam_files, bool print_result_bams, CellsDataContainer &container);
 	const std::vector<TaggedFile> &tagged_files() const { return _tagged; }   // of the last parse_bam_files call
+	// BamController::write_filtered_bam_files (BamController.cpp:38-48; -F), after container.merge_and_filter(): the same files are read again, and
+	// every accepted alignment that FilteringBamProcessor::write_alignment writes -- the container's verdict for it is "written"
+	// (dropest_read_corrections, include/dropest_amd.h) -- goes out with the edits of -b and, behind them, the target cell's barcode
+	// (BamTags::cell_barcode) and the corrected UMI (BamTags::umi) as Z tags (DESIGN.md section 7 has the rule).  As in the reference
+	// (FilteringBamProcessor::update_bam, :103-110: only the first input opens a writer) there is ONE output, `<first input's stem>.filtered.bam`
+	// in the current directory, with the first file's header, and the written records of ALL inputs follow in order.  The records are decoded,
+	// edited and compressed on the device and nothing is added to the container; read i of the container is the i-th record the files'
+	// readers accept, so the files must be the ones the container was filled from, in that order: a window that would pass the container's
+	// read count, or a final count that differs from it, throws std::runtime_error saying so; and when this controller filled the container
+	// (its last parse_bam_files call accepted exactly the container's reads) every file must bring the reads it brought then.  Device path only, like -b: -r parameter files,
+	// gene = chromosome name, a read-type value over 24 bytes, no GPU throw naming the reason; a sharded or split container and UMI-dictionary
+	// mode throw with the read corrections' own message.
+	void write_filtered_bam_files(const std::vector<std::string> &bam_files, CellsDataContainer &container);
+	const FilteredFile &filtered_file() const { return _filtered; }           // of the last write_filtered_bam_files call (empty when it threw)
 	// BGZF inflate, record chain and tag walk on the container's GPU (include/dropest_bgzf.h) where the configuration allows it: tags or read
 	// names as the source of barcode / UMI, the gene tag or a -g annotation (annotation_api.hip) as the source of the gene; not with -r or gene =
 	// chromosome name (the host reader then runs).  A sharded container is fed by one decoder on the GPU of the shard the file's first read goes to.

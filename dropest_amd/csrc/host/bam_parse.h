@@ -299,6 +299,7 @@ struct FileIngest {
 	RecordParser parser;
 	BulkWindow bulk;
 	BamController::TaggedFile *tagged = nullptr;   // -b: this file's tagged BAM is to be written (device path only); what was written is noted here
+	struct FilteredPass *filtered = nullptr;       // -F: the file is read for write_filtered_bam_files -- nothing goes into the container
 	std::string refusal;                 // why the device path handed the file back (read_file_on_device returned false)
 	FileIngest(const BamSwitches &sw, const std::string &bam_name, size_t n_files, CellsDataContainer &container, BamController::Counters &counters,
 	           const BamTags &tags, bool filled_bam, bool params_from_files, bool gene_in_chromosome_name, int min_barcode_phred,
@@ -306,6 +307,16 @@ struct FileIngest {
 		: sw(sw), bam_name(bam_name), n_files(n_files), container(container), counters(counters),
 		  parser(tags, filled_bam, params_from_files, gene_in_chromosome_name, min_barcode_phred, genes, refs, container), bulk(threads, parser, counters) {}
 };
+
+// -F (bam_device.cpp): what the files of one write_filtered_bam_files call share -- the container's decisions on the device, the running count of
+// accepted records, the one output and its compressor.  _open throws what the read corrections refuse; _close(ok): what is left over, the
+// end-of-file block and the account in `report` when ok, else the output is removed and `report` left empty.
+struct FilteredPass;
+FilteredPass *filtered_pass_open(const BamSwitches &sw, CellsDataContainer &container, BamController::FilteredFile &report);
+void filtered_pass_close(FilteredPass *pass, bool ok);
+uint64_t filtered_pass_reads(const FilteredPass *pass);      // accepted records of the files read so far
+uint64_t filtered_pass_total(const FilteredPass *pass);      // the container's reads
+[[noreturn]] void filtered_pass_other_files(const FilteredPass *pass, const std::string &what);
 
 // bam_device.cpp: the file through the GPU (include/dropest_bgzf.h); false: the host reader is to read it, nothing was added
 bool read_file_on_device(FileIngest &file);

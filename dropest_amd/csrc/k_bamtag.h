@@ -22,6 +22,18 @@
 // bam_tag_plan and bam_tag_emit run the SAME function (bamtag_record) once without and once with a destination: the spans the plan finds live in
 // registers and are found again by the emit from bytes that are still in L2, instead of ~100 bytes of spans per record going through memory (a record
 // may drop any number of entries -- a repeated CR -- so a stored plan would need a bound that the rule does not have).
+//
+// The filtered mode (-F: FilteringBamProcessor::write_alignment, FilteringBamProcessor.cpp:61-96) is the same function with FILT = true: a record is
+// written only when the container's verdict for it is 0, and two more tags follow the read type -- the corrected cell barcode and the corrected UMI.
+// The decisions are indexed by the window's ACCEPTED records, so record r takes entry rank[r] = accepted records before r (bam_tag_rank_*: a tile
+// count, a scan of the tiles by one workgroup, a scan inside the tile -- the shape of the size scan below, on the device: no status goes to the
+// host).  The two values exist nowhere as bytes: a plain 2-bit code is spelled by the lanes (base j by lane j, at most 31 of them), an escaped
+// one is a side string copied 64 bytes a step like every other span.  The shape stays for the same reason: the decision costs a wave five
+// wave-uniform loads (rank, verdict, cell, the cell's code, the UMI code) in front of a walk of ~15 entries, and a record that is not written
+// costs nothing else.  Everything a decision points at is checked before it is
+// loaded: a cell id or a side-string index out of range sets BAMTAG_FLAG_RANGE and the record gets size 0.
+// Measured: rank + plan + scan + emit 64.5 ms for 16 M records of which 13.7 M are written (-b in the same job: 59.1 ms for all 16 M);
+// 3-9 % of the -F pass, of which the compressor is 71-81 %.
 #pragma once
 
 #include "k_bamparse.h"
@@ -42,7 +54,21 @@ struct BamTagIn {
 };
 
 constexpr uint32_t BAMTAG_T = 256, BAMTAG_WAVES = BAMTAG_T / 64;
-enum : uint32_t { BAMTAG_FLAG_UNDECIDED = 1u, BAMTAG_FLAG_SIZE = 2u };   // -g left the record's gene to the host; plan and emit disagree (internal)
+constexpr uint32_t BAMTAG_SCAN_PER = 16, BAMTAG_SCAN_TILE = 256 * BAMTAG_SCAN_PER;      // the scans below: records per lane, per workgroup
+// -g left the record's gene to the host; plan and emit disagree (internal); -F: a decision names a cell or a side string that does not exist
+enum : uint32_t { BAMTAG_FLAG_UNDECIDED = 1u, BAMTAG_FLAG_SIZE = 2u, BAMTAG_FLAG_RANGE = 4u };
+
+// -F: the decisions of the window's accepted records (entry rank[r] belongs to record r) and what they point at
+struct BamTagFilt {
+	const uint32_t *rank;                                                 // per record of the window: accepted records before it
+	const uint8_t *verdict; const uint32_t *cell; const uint64_t *umi; uint32_t n;      // per accepted record: 0 = written, target cell, corrected UMI (a code)
+	const uint64_t *cell_barcode; uint32_t n_cells;             // every cell's barcode as a code
+	const uint32_t *side_off; const uint8_t *side_pool; uint32_t n_side;  // the strings of escaped codes: string k = pool[off[k] .. off[k + 1])
+	uint32_t out_tag[2];                                                  // corrected barcode, corrected UMI (0 = never written)
+};
+// a value of -F as the record function takes it: len characters, of a side string (str) or spelled from a plain code
+struct BamTagValue { const uint8_t *str; unsigned long long code; uint32_t len; };
+struct BamTagFix { uint32_t name[2]; BamTagValue v[2]; };
 
 __device__ inline uint32_t bt_u(uint32_t v) { return uint32_t(__builtin_amdgcn_readfirstlane(int(v))); }
 
@@ -100,12 +126,29 @@ template <bool EMIT> struct BamTagOut {
 		}
 		at += n + 4u;
 	}
+	// -F: name, 'Z', a value spelled from its 2-bit code (base j, the first most significant, by lane j) or copied from its side string, NUL
+	__device__ void value(uint32_t name, const BamTagValue &v, uint32_t lane) {
+		const uint32_t n = v.len;
+		if (EMIT) {
+			if (uint64_t(at) + n + 4u > cap) { over = true; return; }
+			for (uint32_t j = lane; j < n + 4u; j += 64) {
+				uint8_t c = 0;
+				if (j == 0) c = uint8_t(name);
+				else if (j == 1) c = uint8_t(name >> 8);
+				else if (j == 2) c = uint8_t('Z');
+				else if (j < n + 3u) c = v.str ? v.str[j - 3u] : uint8_t(0x54474341u >> (8u * (uint32_t(v.code >> (2u * (n + 2u - j))) & 3u)));      // "ACGT"
+				dst[at + j] = c;
+			}
+		}
+		at += n + 4u;
+	}
 };
 
 // Record `rec` (its block_size field first, accepted by bam_parse) -> the bytes of its output (block_size field included), counted or written.
-template <bool EMIT>
+// FILT (-F): the two values of `fx` follow the read type, under the same rule (a value of no character is not written and drops nothing).
+template <bool EMIT, bool FILT = false>
 __device__ inline uint32_t bamtag_record(const uint8_t *rec, uint32_t lane, const BamParseCfg &pc, const BamTagCfg &tc, uint32_t mark, const uint8_t *gene_override, uint32_t gene_override_len,
-                                         bool use_override, uint8_t *dst, uint32_t cap, bool &over) {
+                                         bool use_override, uint8_t *dst, uint32_t cap, bool &over, const BamTagFix &fx = BamTagFix{}) {
 	const uint32_t block_size = bt_u(b_le32(rec));
 	const uint8_t *p = rec + 4;
 	const uint32_t l_read_name = bt_u(p[8]), n_cigar = bt_u(b_le16(p + 12)), l_seq = bt_u(b_le32(p + 16));
@@ -158,14 +201,16 @@ __device__ inline uint32_t bamtag_record(const uint8_t *rec, uint32_t lane, cons
 	if (use_override) { src[0] = gene_override; sl[0] = gene_override_len; }
 	else if (found[T_GENE]) { src[0] = val[T_GENE]; sl[0] = vlen[T_GENE]; }
 	const int type_k = mark == 2u ? 0 : mark == 4u ? 1 : mark == 1u ? 2 : -1;      // exactly exonic / intronic / intergenic; a spanning mark writes none
-	bool on[6];
+	constexpr int NT = FILT ? 8 : 6;
+	bool on[NT];
 	on[0] = sl[0] != 0; on[1] = true; on[2] = true; on[3] = sl[3] != 0; on[4] = sl[4] != 0; on[5] = type_k >= 0;
-	uint32_t ename[6];
+	uint32_t ename[NT];
 #pragma unroll
 	for (int k = 0; k < 5; ++k) ename[k] = tc.out_tag[k];
 	ename[5] = tc.type_tag;
+	if (FILT) { on[NT - 2] = fx.v[0].len != 0; on[NT - 1] = fx.v[1].len != 0; ename[NT - 2] = fx.name[0]; ename[NT - 1] = fx.name[1]; }
 #pragma unroll
-	for (int k = 0; k < 6; ++k) on[k] = on[k] && ename[k] != 0u;      // a tag without a name is never written (and drops nothing)
+	for (int k = 0; k < NT; ++k) on[k] = on[k] && ename[k] != 0u;      // a tag without a name is never written (and drops nothing)
 	// 3. the output: block_size, the bytes before the aux data, the runs of kept entries, the bytes the walk did not reach, the new tags
 	BamTagOut<EMIT> out{dst, 4u, cap, false};
 	out.copy(p, aux, lane);
@@ -176,7 +221,7 @@ __device__ inline uint32_t bamtag_record(const uint8_t *rec, uint32_t lane, cons
 		if (!bamtag_entry(tags, tags_size, o, lane, name, type, len, text)) break;      // (never before walk_end: the same walk)
 		bool drop = false;
 #pragma unroll
-		for (int k = 0; k < 6; ++k) drop |= on[k] && ename[k] == name;
+		for (int k = 0; k < NT; ++k) drop |= on[k] && ename[k] == name;
 		if (drop) { out.copy(tags + run, o - run, lane); run = o + 3u + len; }
 		o += 3u + len;
 	}
@@ -184,6 +229,10 @@ __device__ inline uint32_t bamtag_record(const uint8_t *rec, uint32_t lane, cons
 #pragma unroll
 	for (int k = 0; k < 5; ++k) if (on[k]) out.tag(ename[k], src[k], sl[k], lane);
 	if (on[5]) out.tag(ename[5], tc.type_val[type_k], tc.type_len[type_k], lane);
+	if (FILT) {
+		if (on[NT - 2]) out.value(ename[NT - 2], fx.v[0], lane);
+		if (on[NT - 1]) out.value(ename[NT - 1], fx.v[1], lane);
+	}
 	if (EMIT) {
 		const uint32_t new_block = out.at - 4u;
 		if (lane < 4u && cap >= 4u) dst[lane] = uint8_t(new_block >> (8u * lane));
@@ -243,8 +292,125 @@ __global__ __launch_bounds__(BAMTAG_T) void bam_tag_emit_kernel(BamTagIn in, Bam
 	if (over && lane == 0) atomicOr(flags, BAMTAG_FLAG_SIZE);
 }
 
+// ---- -F: a record's decision ------------------------------------------------------------------------------------------------------------
+__device__ inline unsigned long long bt_u64(unsigned long long v) { return (unsigned long long)bt_u(uint32_t(v)) | ((unsigned long long)bt_u(uint32_t(v >> 32)) << 32); }
+
+// a code -> the value to write; false: an escaped code whose side string does not exist (nothing of it is loaded)
+__device__ inline bool bamtag_value(unsigned long long code, const BamTagFilt &f, BamTagValue &v) {
+	v.str = nullptr; v.code = code; v.len = 0;
+	if (code >> 63) {
+		const unsigned long long k = code & 0x7FFFFFFFFFFFFFFFull;
+		if (k >= f.n_side) return false;
+		const uint32_t a = bt_u(f.side_off[k]), b = bt_u(f.side_off[k + 1]);
+		v.str = f.side_pool + a; v.len = b > a ? b - a : 0u;
+	} else if (code)
+		v.len = uint32_t(63 - __clzll((long long)code)) / 2u;      // the sentinel bit says how many bases follow it
+	return true;
+}
+
+// Record r of the window: false = not written (not accepted, or a verdict that is not 0, or a decision that points outside its tables: flagged)
+__device__ inline bool bamtag_decision(const BamTagIn &in, const BamTagFilt &f, uint32_t r, BamTagFix &fx, uint32_t *flags, uint32_t lane) {
+	if (bt_u(in.status[r]) != BAM_OK) return false;
+	const uint32_t k = bt_u(f.rank[r]);
+	bool ok = k < f.n;                                             // (always: the caller checked the window's accepted count)
+	if (ok && bt_u(f.verdict[k]) != 0u) return false;
+	uint32_t cell = 0;
+	if (ok) { cell = bt_u(f.cell[k]); ok = cell < f.n_cells; }
+	if (ok) ok = bamtag_value(bt_u64(f.cell_barcode[cell]), f, fx.v[0]);
+	if (ok) ok = bamtag_value(bt_u64(f.umi[k]), f, fx.v[1]);
+	if (!ok) { if (lane == 0) atomicOr(flags, BAMTAG_FLAG_RANGE); return false; }
+	fx.name[0] = f.out_tag[0]; fx.name[1] = f.out_tag[1];
+	return true;
+}
+
+// bam_tag_plan_kernel / bam_tag_emit_kernel for -F
+__global__ __launch_bounds__(BAMTAG_T) void bam_tag_filter_plan_kernel(BamTagIn in, BamParseCfg pc, BamTagCfg tc, BamTagNames names, BamTagFilt filt, uint32_t *__restrict__ size,
+                                                                        uint32_t *__restrict__ flags) {
+	const uint32_t lane = threadIdx.x & 63u;
+	const uint32_t r = bt_u(blockIdx.x * BAMTAG_WAVES + (threadIdx.x >> 6));
+	if (r >= in.n_rec) return;
+	uint32_t mark, g_len; const uint8_t *g; bool use_override, over = false;
+	uint32_t bytes = 0;
+	BamTagFix fx;
+	if (bamtag_decision(in, filt, r, fx, flags, lane) && bamtag_inputs(in, names, r, mark, g, g_len, use_override, flags, lane))
+		bytes = bamtag_record<false, true>(in.data + in.rec_off[r], lane, pc, tc, mark, g, g_len, use_override, nullptr, 0u, over, fx);
+	if (lane == 0) size[r] = bytes;
+}
+
+__global__ __launch_bounds__(BAMTAG_T) void bam_tag_filter_emit_kernel(BamTagIn in, BamParseCfg pc, BamTagCfg tc, BamTagNames names, BamTagFilt filt, const uint32_t *__restrict__ size,
+                                                                        const uint64_t *__restrict__ out_off, uint8_t *__restrict__ out, uint64_t out_total, uint32_t *__restrict__ flags) {
+	const uint32_t lane = threadIdx.x & 63u;
+	const uint32_t r = bt_u(blockIdx.x * BAMTAG_WAVES + (threadIdx.x >> 6));
+	if (r >= in.n_rec) return;
+	const uint32_t cap = bt_u(size[r]);
+	if (!cap) return;
+	const uint64_t at = out_off[r];
+	if (at + cap > out_total) { if (lane == 0) atomicOr(flags, BAMTAG_FLAG_SIZE); return; }
+	uint32_t mark, g_len; const uint8_t *g; bool use_override, over = false;
+	BamTagFix fx;
+	if (!bamtag_decision(in, filt, r, fx, flags, lane) || !bamtag_inputs(in, names, r, mark, g, g_len, use_override, flags, lane)) return;
+	bamtag_record<true, true>(in.data + in.rec_off[r], lane, pc, tc, mark, g, g_len, use_override, out + at, cap, over, fx);
+	if (over && lane == 0) atomicOr(flags, BAMTAG_FLAG_SIZE);
+}
+
+// ---- -F: rank[r] = accepted records of the window before r, in the three steps of the size scan below ---------------------------------------
+// tile_ok[t] = accepted records in tile t of 4 096 records
+__global__ __launch_bounds__(256) void bam_tag_rank_tile_kernel(const uint8_t *__restrict__ status, uint32_t n, uint32_t *__restrict__ tile_ok) {
+	__shared__ uint32_t s_ok;
+	if (threadIdx.x == 0) s_ok = 0;
+	__syncthreads();
+	const uint32_t first = blockIdx.x * BAMTAG_SCAN_TILE + threadIdx.x * BAMTAG_SCAN_PER;
+	uint32_t ok = 0;
+	for (uint32_t j = 0; j < BAMTAG_SCAN_PER && first + j < n; ++j) ok += status[first + j] == BAM_OK ? 1u : 0u;
+	if (ok) atomicAdd(&s_ok, ok);
+	__syncthreads();
+	if (threadIdx.x == 0) tile_ok[blockIdx.x] = s_ok;
+}
+
+// exclusive scan of the tiles' counts by ONE workgroup; total[0] = the window's accepted records
+__global__ __launch_bounds__(1024) void bam_tag_rank_scan_kernel(uint32_t *__restrict__ tile_ok, uint32_t n, uint32_t *__restrict__ total) {
+	__shared__ uint32_t sa[1024];
+	__shared__ uint32_t carry;
+	if (threadIdx.x == 0) carry = 0;
+	__syncthreads();
+	for (uint32_t base = 0; base < n; base += 1024) {
+		const uint32_t i = base + threadIdx.x;
+		const uint32_t va = i < n ? tile_ok[i] : 0u;
+		sa[threadIdx.x] = va;
+		__syncthreads();
+		for (uint32_t dd = 1; dd < 1024; dd <<= 1) {
+			const uint32_t xa = threadIdx.x >= dd ? sa[threadIdx.x - dd] : 0u;
+			__syncthreads();
+			sa[threadIdx.x] += xa;
+			__syncthreads();
+		}
+		if (i < n) tile_ok[i] = carry + sa[threadIdx.x] - va;
+		__syncthreads();
+		if (threadIdx.x == 1023) carry += sa[1023];
+		__syncthreads();
+	}
+	if (threadIdx.x == 0) total[0] = carry;
+}
+
+// rank[r] = the tile's base + the accepted records of the tile before r
+__global__ __launch_bounds__(256) void bam_tag_rank_kernel(const uint8_t *__restrict__ status, uint32_t n, const uint32_t *__restrict__ tile_base, uint32_t *__restrict__ rank) {
+	__shared__ uint32_t s[256];
+	const uint32_t first = blockIdx.x * BAMTAG_SCAN_TILE + threadIdx.x * BAMTAG_SCAN_PER;
+	uint32_t mine = 0;
+	for (uint32_t j = 0; j < BAMTAG_SCAN_PER && first + j < n; ++j) mine += status[first + j] == BAM_OK ? 1u : 0u;
+	s[threadIdx.x] = mine;
+	__syncthreads();
+	for (uint32_t dd = 1; dd < 256; dd <<= 1) {
+		const uint32_t x = threadIdx.x >= dd ? s[threadIdx.x - dd] : 0u;
+		__syncthreads();
+		s[threadIdx.x] += x;
+		__syncthreads();
+	}
+	uint32_t at = tile_base[blockIdx.x] + s[threadIdx.x] - mine;
+	for (uint32_t j = 0; j < BAMTAG_SCAN_PER && first + j < n; ++j) { rank[first + j] = at; at += status[first + j] == BAM_OK ? 1u : 0u; }
+}
+
 // ---- the exclusive scan over the sizes: 64-bit offsets, as rec_off ----------------------------------------------------------------------
-constexpr uint32_t BAMTAG_SCAN_PER = 16, BAMTAG_SCAN_TILE = 256 * BAMTAG_SCAN_PER;
 // bytes and records written per tile of 4 096 records
 __global__ __launch_bounds__(256) void bam_tag_tile_sum_kernel(const uint32_t *__restrict__ size, uint32_t n, unsigned long long *__restrict__ tile_bytes, uint32_t *__restrict__ tile_written) {
 	__shared__ unsigned long long s_bytes;

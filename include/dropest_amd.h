@@ -218,6 +218,9 @@ dropest_status dropest_read_corrections(dropest_ctx *ctx, uint64_t *n, const uin
                                         const uint64_t **d_umi);
 dropest_status dropest_read_corrections_host(dropest_ctx *ctx, uint64_t first, uint64_t count, uint8_t *verdict, uint32_t *cell, uint64_t *umi);
 dropest_status dropest_read_correction_counts(dropest_ctx *ctx, uint64_t out[5]);
+/* Every cell's barcode in the packed / escaped form of the way in, by cell id -- what a corrections' `cell` entry stands for: a DEVICE array of
+ * *n = total cells, owned by the context and valid as long as the read corrections are.  Refused where dropest_read_corrections is. */
+dropest_status dropest_cell_barcodes_device(dropest_ctx *ctx, uint64_t *n, const uint64_t **d_codes);
 /* CellsDataContainer::add_umi_to_cell (CellsDataContainer.h:90, CellsDataContainer.cpp:356-364) on the initialised container:
  * one more read of `umi_code` (packed as on the way in) for gene index `gene` in cell `cell` with mark bits `mark` --
  * Gene::add_umi: a new molecule (TOTAL_UMIS_PER_CB + 1) or read_count + 1 / mark OR of the existing one; like the reference's

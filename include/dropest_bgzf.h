@@ -191,6 +191,32 @@ int dropest_bam_decoder_tagged_to_host(dropest_bam_decoder *d, uint8_t *dst, uin
 /* Since the decoder was created or reset: the time of the tag kernels (plan, scan, emit) by device events, the inflated bytes of the windows
  * they looked at and the bytes they wrote (waits for the last emit).  Any pointer may be NULL. */
 int dropest_bam_decoder_tag_stats(dropest_bam_decoder *d, double *kernel_ms, uint64_t *bytes_in, uint64_t *bytes_out);
+/* ---- -F: filtered BAM output (the filtered mode of csrc/k_bamtag.h; DESIGN.md section 7 has the rule) ---------------------------------------------------
+ * What FilteringBamProcessor::write_alignment (FilteringBamProcessor.cpp:61-96) writes: an accepted alignment only when the container's verdict for
+ * it is 0 (dropest_read_corrections, dropest_amd.h), through the same save_alignment -- the edits of -b, then the corrected cell barcode (the target
+ * cell's) and the corrected UMI as two more Z tags behind the read type, under the same rule; a value of no character writes no tag and drops none.
+ * The values are packed codes of dropest_amd.h (plain, or DROPEST_ESCAPE | k for side string k); the kernels spell them. */
+typedef struct dropest_bam_filter_cfg {
+	uint16_t out_tag[2];                 /* corrected cell barcode ("CB"), corrected UMI ("UB"): letters lo | hi << 8, 0 = never written */
+	uint32_t on_device;                  /* cell_barcode is DEVICE memory of the decoder's GPU that stays valid while filtering is on; 0: host memory, copied */
+	const uint64_t *cell_barcode;        /* every cell's barcode as a code, by cell id */
+	uint32_t n_cells;
+	uint32_t n_side;                     /* the strings of escaped codes, string k = side_pool[side_off[k] .. side_off[k + 1]); HOST memory, copied */
+	const uint32_t *side_off;
+	const uint8_t *side_pool;
+} dropest_bam_filter_cfg;
+/* After dropest_bam_decoder_set_tagging, from which the other six tags come (a later _set_tagging turns filtering off again, as a reset does).  NULL
+ * turns it off.  Refused: two output tags with one name. */
+int dropest_bam_decoder_set_filtering(dropest_bam_decoder *d, const dropest_bam_filter_cfg *cfg);
+/* The filtered twin of .._tag_window for the LAST window.  verdict / cell / umi: the decisions of the window's accepted records in file order --
+ * entry k belongs to the k-th accepted record; n must be the window's n_accepted.  on_device != 0: device arrays (dropest_read_corrections'
+ * pointers offset to the window's first accepted read); 0: host arrays, uploaded through the decoder's pinned staging.  Which record takes which
+ * entry is found on the device.  *len = 0 and *n_written = 0 when no read of the window is written.  Returns as .._tag_window does (2: -g left
+ * genes to the host; .._patch_annotation, then call again); 1 as well when the decision of a read that is written names a cell >= n_cells or a
+ * side string >= n_side (nothing is loaded from there, nothing is written).  The bytes: *d_out, or .._tagged_to_host.  .._tag_window on the same
+ * window afterwards still gives the -b bytes. */
+int dropest_bam_decoder_filter_window(dropest_bam_decoder *d, const uint8_t *verdict, const uint32_t *cell, const uint64_t *umi, uint64_t n, int on_device,
+                                      const uint8_t **d_out, uint64_t *len, uint64_t *n_written);
 /* The hipStream_t the decoder's kernels run on (lent or its own): work a caller queues there follows the tagged bytes in order. */
 void *dropest_bam_decoder_stream(dropest_bam_decoder *d);
 
