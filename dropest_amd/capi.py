@@ -227,6 +227,11 @@ def lib():
         "dropest_shard_merge_validation_samples": (C.c_int, [vp, P(ValidationOpts), P(ValidationSample), C.c_uint32]),
         "dropest_shard_group_merge_validation_samples": (C.c_int, [vp, C.c_int32, P(ValidationOpts), P(ValidationSample), C.c_uint32]),
         "dropest_validation_cut_pairs": (C.c_int, [vp, C.c_uint64, C.c_int32, vp]),
+        "dropest_shard_read_corrections": (C.c_int, [vp, u64p, u64p, P(vp), P(vp), P(vp)]),
+        "dropest_shard_group_read_corrections": (C.c_int, [vp, C.c_int32]),
+        "dropest_shard_group_read_corrections_host": (C.c_int, [vp, C.c_int32, C.c_uint64, C.c_uint64, vp, vp, vp]),
+        "dropest_shard_group_read_correction_counts": (C.c_int, [vp, C.c_int32, vp]),
+        "dropest_shard_filtered_barcodes_device": (C.c_int, [vp, u64p, P(vp)]),
         "dropest_shard_matrix": (C.c_int, [vp, C.c_int, u64p, u64p, P(vp), P(vp), P(vp), P(vp)]),
         "dropest_shard_matrix_form": (C.c_int, [vp, C.c_int, P(C.c_int32)]),
         "dropest_shard_matrix_narrow": (C.c_int, [vp, C.c_int, u64p, u64p, P(vp), P(vp), P(vp), P(vp), u64p, P(vp), P(vp)]),
@@ -276,6 +281,8 @@ EXPORTED_SYMBOLS = [
     "dropest_debug_poison_scratch", "dropest_debug_trim_pool", "dropest_debug_alloc_ordinal", "dropest_debug_alloc_site",
     "dropest_set_save_umi_merge_targets", "dropest_umi_merge_targets", "dropest_read_corrections", "dropest_read_corrections_host",
     "dropest_read_correction_counts", "dropest_cell_barcodes_device",
+    "dropest_shard_read_corrections", "dropest_shard_group_read_corrections", "dropest_shard_group_read_corrections_host",
+    "dropest_shard_group_read_correction_counts", "dropest_shard_filtered_barcodes_device",
 ]
 
 

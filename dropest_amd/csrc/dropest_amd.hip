@@ -2377,7 +2377,8 @@ dropest_status dropest_merge_umis(dropest_ctx *ctx, uint64_t cell, uint32_t gene
 dropest_status dropest_set_save_umi_merge_targets(dropest_ctx *ctx, int enabled) {
 	return guarded([&] {
 		if (!ctx) throw InvalidError("null context");
-		if (ctx->merged) throw InvalidError("save_umi_merge_targets must be set before merge_and_filter");
+		// (a shard's context is emptied by its next step: the setting is for that step)
+		if (ctx->merged && !ctx->is_shard_ctx) throw InvalidError("save_umi_merge_targets must be set before merge_and_filter");
 		ctx->save_umi_targets = enabled != 0;
 	});
 }

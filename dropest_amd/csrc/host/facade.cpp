@@ -2,6 +2,7 @@
 #include "facade.h"
 #include "rds_writer.h"
 #include "../../../include/dropest_deflate.h"
+#include "../../../include/dropest_synth.h"
 
 #include <algorithm>
 #include <atomic>
@@ -149,6 +150,7 @@ CellsDataContainer::CellsDataContainer(const std::shared_ptr<Merge::MergeStrateg
 	_shards.assign(devices.size(), nullptr);
 	_shard_devices = devices;
 	check(dropest_shard_group_create(&cfg, int32_t(dev.size()), dev.data(), _shards.data()));
+	for (dropest_shard *s : _shards) check(dropest_set_save_umi_merge_targets(dropest_shard_ctx(s), _save_umi_merge_targets));
 }
 
 void CellsDataContainer::send_side_strings(dropest_ctx *ctx) const {
@@ -228,6 +230,29 @@ std::vector<std::pair<std::string, std::string>> CellsDataContainer::merged_barc
 	for (size_t i = 0; i < t.size(); ++i) if (t[i] != i) out.emplace_back(cell(i).barcode(), cell(t[i]).barcode());
 	std::sort(out.begin(), out.end());
 	return out;
+}
+
+void CellsDataContainer::read_corrections_host(uint64_t first, uint64_t count, uint8_t *verdict, uint64_t *target_barcode_code, uint64_t *umi) const {
+	if (!_is_initialized) throw std::runtime_error("You must initialize container");
+	std::vector<uint32_t> index(target_barcode_code ? size_t(count) : 0);
+	uint64_t n_codes = 0;
+	const uint64_t *d_codes = nullptr;
+	int device = _device;
+	if (sharded()) {   // `index` = columns of the filtered matrix
+		check(dropest_shard_group_read_corrections_host(_shards.data(), int32_t(_shards.size()), first, count, verdict, index.empty() ? nullptr : index.data(), umi));
+		if (target_barcode_code) check(dropest_shard_filtered_barcodes_device(_shards[0], &n_codes, &d_codes));
+		if (!_shard_devices.empty()) device = _shard_devices[0];
+	} else {           // `index` = cell ids
+		check(dropest_read_corrections_host(_ctx, first, count, verdict, index.empty() ? nullptr : index.data(), umi));
+		if (target_barcode_code) check(dropest_cell_barcodes_device(_ctx, &n_codes, &d_codes));
+	}
+	if (!target_barcode_code) return;
+	std::vector<uint64_t> codes(static_cast<size_t>(n_codes));
+	if (n_codes && dropest_dev_copy_to_host(device, codes.data(), d_codes, n_codes * 8) != 0) throw std::runtime_error("the barcode table could not be copied from the device");
+	for (uint64_t i = 0; i < count; ++i) {
+		if (index[i] != 0xFFFFFFFFu && index[i] >= n_codes) throw std::runtime_error("internal: a read's target lies outside the barcode table");
+		target_barcode_code[i] = index[i] == 0xFFFFFFFFu ? 0 : codes[index[i]];
+	}
 }
 
 void CellsDataContainer::add_record(const ReadInfo &r) {   // CellsDataContainer.cpp:59-88

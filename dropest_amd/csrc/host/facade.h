@@ -491,8 +491,15 @@ public:
 	void merge_cells(size_t source_cell_ind, size_t target_cell_ind);
 	void merge_umis(size_t cell_id, size_t gene, const s_s_hash_t &merge_targets);                  // RealBarcodesMergeStrategy::get_merge_target
 	// cell(cell_id).genes().at(gene).merge_targets() (Gene.h; Gene.cpp:54-57, :124-127): {source UMI: target UMI} of the UMI merges applied to
-	// that gene of that cell; empty unless the container was made with save_umi_merge_targets (one GPU: the sharded container ignores the flag)
+	// that gene of that cell; empty unless the container was made with save_umi_merge_targets (one GPU: a sharded container keeps the targets
+	// for read_corrections_host only, its cells have no ids)
 	s_s_hash_t umi_merge_targets(size_t cell_id, size_t gene) const;
+	// What FilteringBamProcessor::write_alignment decides for reads [first, first + count) of the stream, in add_record order, on the state the
+	// container is in (dropest_read_corrections_host; sharded or split: dropest_shard_group_read_corrections_host, after merge_and_filter).
+	// verdict: 0 written, 1 no gene, 2 cell not kept, 3 wrong gene, 4 wrong UMI; target_barcode_code: the corrected CB as a packed / escaped
+	// code, 0 where there is none (verdicts 1, 2); umi: the corrected UB as a code.  The same answer from both kinds of container.  Any
+	// output pointer may be null.
+	void read_corrections_host(uint64_t first, uint64_t count, uint8_t *verdict, uint64_t *target_barcode_code, uint64_t *umi) const;
 	bool save_umi_merge_targets() const { return _save_umi_merge_targets; }
 	// CellsDataContainer.h:90 (CellsDataContainer.cpp:356-364): one more read of read_info's UMI for read_info's gene in cell
 	// `cell_id` -- a new molecule (TOTAL_UMIS_PER_CB + 1) or read count + 1 / mark OR; no read counters, no chromosome statistics.

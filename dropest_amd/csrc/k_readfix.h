@@ -29,6 +29,13 @@
 //   diverge   reads that fail tests 1-2 leave their lane idle while the others search.  Compacting the survivors first would cost a pass of
 //             its own over a stream where at least a quarter, usually most, of the reads survive: not done.
 //   counts    one count per verdict: every lane keeps five wave-uniform sums (ballots), lane 0 of each wave adds them once at the end.
+//   look-up   the step barcode -> rank is the kernel's template parameter.  RfOwnCells: the one context's, as above.  RfColumnTable: a shard
+//             of a sharded run (shard_read_corrections.h) sees reads whose barcodes other shards own, so it asks a table that every shard
+//             holds alike: barcode -> column of cm, one open-addressed probe of a 16-byte slot {barcode, column, set}, hashed with mix64 and
+//             probed linearly like the pass's own table; key 0 is the empty slot (a packed code carries a sentinel bit, an escaped one bit
+//             63).  rank = column = what is written as the target, so rank -> cell id falls away.  bc_insert_kernel builds the table: a
+//             barcode that arrives with two different columns raises a flag, nothing is overwritten.  The table is kept cells plus their
+//             merged sources -- tens of thousands of slots, L2-resident -- and lives in global memory only.
 #pragma once
 
 #include "k_cbhash.h"
@@ -37,6 +44,14 @@ namespace dropest {
 
 constexpr uint32_t RF_NONE = 0xFFFFFFFFu;
 enum : uint8_t { RF_WRITTEN = 0, RF_NO_GENE = 1, RF_CELL_NOT_KEPT = 2, RF_WRONG_GENE = 3, RF_WRONG_UMI = 4 };
+
+// barcode -> column of cm, replicated on every shard.  `set`: 0 = no column yet, 1 = column written (one 64-bit word with it: one CAS)
+struct BcColSlot {
+	unsigned long long key;                      // barcode code, 0 = empty
+	uint32_t column;
+	uint32_t set;
+};
+static_assert(sizeof(BcColSlot) == 16, "slot layout");
 
 struct ReadFixArgs {
 	const unsigned long long *cb, *umi;          // the resident columns
@@ -57,6 +72,64 @@ struct ReadFixArgs {
 	uint32_t *cell;                              // target cell id; RF_NONE for verdicts 1 and 2
 	unsigned long long *umi_out;                 // corrected UMI (verdict 0), the read's own otherwise
 	unsigned long long *counts;                  // [5], zeroed by the caller
+	// RfColumnTable only (behind everything RfOwnCells reads: that instantiation's argument offsets stay what they were)
+	const BcColSlot *bc_slots;
+	uint32_t bc_mask;                            // capacity - 1
+};
+
+struct BcPair { unsigned long long barcode; uint32_t column, pad; };   // what the shards gather: one per own cell whose target is a column
+static_assert(sizeof(BcPair) == 16, "pair layout");
+
+enum : uint32_t { BC_FLAG_DUPLICATE = 1u, BC_FLAG_FULL = 2u, BC_FLAG_BAD_KEY = 4u };
+
+// One lane per (barcode, column) pair.  capacity = mask + 1 is a power of two of at least twice n, so a free slot always exists; the probe
+// is bounded by the capacity all the same.  flags: BC_FLAG_* of what went wrong (the host turns any of them into an error).
+__global__ __launch_bounds__(256) void bc_insert_kernel(const BcPair *__restrict__ pairs, uint32_t n, BcColSlot *slots, uint32_t mask, uint32_t *flags) {
+	const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+	if (i >= n) return;
+	const unsigned long long k = pairs[i].barcode;
+	if (k == 0ull) { atomicOr(flags, BC_FLAG_BAD_KEY); return; }
+	const unsigned long long mine = (1ull << 32) | pairs[i].column;   // {column, set = 1} as the slot's second word
+	uint32_t h = uint32_t(mix64(k)) & mask;
+	for (uint32_t probe = 0; probe <= mask; ++probe, h = (h + 1) & mask) {
+		unsigned long long cur = slots[h].key;
+		if (cur == 0ull) cur = atomicCAS(&slots[h].key, 0ull, k);   // (the CAS's answer is the authority; 0: the slot is mine now)
+		if (cur != 0ull && cur != k) continue;
+		const unsigned long long was = atomicCAS(reinterpret_cast<unsigned long long *>(&slots[h].column), 0ull, mine);
+		if (was != 0ull && was != mine) atomicOr(flags, BC_FLAG_DUPLICATE);
+		return;
+	}
+	atomicOr(flags, BC_FLAG_FULL);
+}
+
+__device__ inline uint32_t bc_find(const BcColSlot *__restrict__ slots, uint32_t mask, unsigned long long k) {   // the column, RF_NONE if absent
+	uint32_t h = uint32_t(mix64(k)) & mask;
+	for (uint32_t probe = 0; probe <= mask; ++probe, h = (h + 1) & mask) {
+		const unsigned long long cur = slots[h].key;
+		if (cur == k) return slots[h].column;
+		if (cur == 0ull) return 0xFFFFFFFFu;
+	}
+	return 0xFFFFFFFFu;
+}
+
+// (test hook and nothing else: the columns of `n` barcodes, one lane each)
+__global__ __launch_bounds__(256) void bc_probe_kernel(const unsigned long long *__restrict__ barcode, uint32_t n, const BcColSlot *__restrict__ slots, uint32_t mask,
+                                                       uint32_t *__restrict__ column) {
+	const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+	if (i < n) column[i] = barcode[i] ? bc_find(slots, mask, barcode[i]) : 0xFFFFFFFFu;
+}
+
+// barcode -> rank among the kept cells, and rank -> what is written as the read's target
+struct RfOwnCells {      // one context: the pass's barcode table, the cells' ranks, the kept cells' ids
+	__device__ static uint32_t rank(const ReadFixArgs &a, unsigned long long cb) {
+		const uint32_t s = cb_find(a.table, cb);
+		return s == 0xFFFFFFFFu ? 0xFFFFFFFFu : a.cell_rank[a.table.slots[s].cell_id];
+	}
+	__device__ static uint32_t target(const ReadFixArgs &a, uint32_t rank) { return a.kept_cell[rank]; }
+};
+struct RfColumnTable {   // a shard: the replicated table; the rank IS the column of cm
+	__device__ static uint32_t rank(const ReadFixArgs &a, unsigned long long cb) { return cb ? bc_find(a.bc_slots, a.bc_mask, cb) : 0xFFFFFFFFu; }
+	__device__ static uint32_t target(const ReadFixArgs &, uint32_t rank) { return rank; }
 };
 
 __device__ inline uint32_t rf_lower_bound(const unsigned long long *__restrict__ k, uint32_t lo, uint32_t hi, unsigned long long want) {
@@ -67,6 +140,7 @@ __device__ inline uint32_t rf_lower_bound(const unsigned long long *__restrict__
 	return lo;
 }
 
+template <class Lookup>
 __global__ __launch_bounds__(256) void read_corrections_kernel(ReadFixArgs a) {
 	uint32_t c0 = 0, c1 = 0, c2 = 0, c3 = 0, c4 = 0;   // wave-uniform
 	const size_t stride = size_t(gridDim.x) * 256u;
@@ -81,10 +155,9 @@ __global__ __launch_bounds__(256) void read_corrections_kernel(ReadFixArgs a) {
 			v = RF_NO_GENE;
 			if (g != NO_GENE) {
 				v = RF_CELL_NOT_KEPT;
-				const uint32_t s = cb_find(a.table, a.cb[i]);
-				const uint32_t rank = s == 0xFFFFFFFFu ? RF_NONE : a.cell_rank[a.table.slots[s].cell_id];
+				const uint32_t rank = Lookup::rank(a, a.cb[i]);
 				if (rank != RF_NONE) {
-					cell = a.kept_cell[rank];
+					cell = Lookup::target(a, rank);
 					v = RF_WRONG_GENE;
 					if (g < a.gene_none) {
 						const uint32_t b = a.mol_begin[rank], e = a.mol_end[rank];

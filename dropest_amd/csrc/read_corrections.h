@@ -70,8 +70,8 @@ const std::vector<dropest_ctx::UmiTargetRow> &dropest_ctx::umi_merge_target_rows
 
 void dropest_ctx::build_read_corrections() {
 	using namespace dropest;
-	if (is_shard_ctx) throw UnsupportedError("read corrections are not computed by one context of a sharded run: this context belongs to a shard");
-	if (was_split) throw UnsupportedError("read corrections are not computed by a split context: dropest_ctx_split handed this context's reads to shards");
+	if (is_shard_ctx) throw UnsupportedError("read corrections are not computed by one context of a sharded run: this context belongs to a shard -- call dropest_shard_read_corrections on every shard, or dropest_shard_group_read_corrections");
+	if (was_split) throw UnsupportedError("read corrections are not computed by a split context: dropest_ctx_split handed this context's reads to shards -- call dropest_shard_group_read_corrections on them");
 	if (!initialized) throw InvalidError("You must initialize container");
 	if (umi_dict_on) throw UnsupportedError("read corrections are not computed in UMI-dictionary mode: the keys carry UMI ranks, not UMI codes");
 	ReadCorrections &R = corrections;
@@ -186,10 +186,10 @@ void dropest_ctx::build_read_corrections() {
 	a.src_key = src_sorted; a.src_target = s_tgt.p; a.src_begin = d_sb.p; a.src_end = d_se.p; a.n_src = n_src;
 	a.gene_bits = L.gene_bits; a.umi_bits = L.umi_bits; a.gene_none = L.gene_none; a.umi_strip_mask = L.umi_strip_mask; a.umi_escape_base = L.umi_escape_base;
 	a.verdict = R.verdict.p; a.cell = R.cell.p; a.umi_out = R.umi.p; a.counts = d_counts.p;
-	static const u32 grid_max = resident_grid(read_corrections_kernel, 256, ~0u);
+	static const u32 grid_max = resident_grid(read_corrections_kernel<RfOwnCells>, 256, ~0u);
 	// algorithmic bytes: 20 in and 13 out per read, one 16-byte table slot, the rank word (the searches' dependent loads are not counted)
 	timed("read_corrections", double(n) * (20 + 13 + 16 + 4), [&] {
-		hipLaunchKernelGGL(read_corrections_kernel, dim3(std::min<u32>(div_up(n, 256), grid_max)), dim3(256), 0, stream, a);
+		hipLaunchKernelGGL(read_corrections_kernel<RfOwnCells>, dim3(std::min<u32>(div_up(n, 256), grid_max)), dim3(256), 0, stream, a);
 	});
 	fetch(R.counts, d_counts.p, 5 * 8);   // (waits: the local buffers above outlive the kernel)
 	R.valid = true;

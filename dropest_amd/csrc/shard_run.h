@@ -14,7 +14,8 @@
 // without a whitelist: shard_merge_free.h) -> UMI merge (N-UMIs: random fills follow ONE rand() sequence in global cell order)
 // and filter -> global column order -> every shard writes ITS columns of both matrices into host memory shared by the node's
 // shards (all PCIe links at once; shard_matrix.h).  The small kernels are in k_shard.h, the transports' test hooks in transport_test.h.
-// After a step: the merge validation statistics (-S) over all shards' filtered cells, shard_validation.h.
+// After a step: the merge validation statistics (-S) over all shards' filtered cells, shard_validation.h; what became of every resident read
+// (-F, the decisions), shard_read_corrections.h.
 #pragma once
 
 #include "transport.h"
@@ -212,10 +213,31 @@ struct dropest_shard {
 	void install_umi_hooks();
 	// merge validation statistics over all shards (shard_validation.h); COLLECTIVE
 	bool stepped = false;
+	// sorted keys column of cm | gene | field of ALL shards' filtered cells, placed by column (shard_validation.h): what -S and the read corrections share
+	struct GlobalKeys {
+		dropest::DevBuf<u64> key, val;           // [n + 1]; val: only when values travelled beside the keys
+		u32 n = 0, F = 0;
+		int gene_bits = 0, umi_bits = 0;
+		bool any_rows = false;                   // some shard had rows: gene_bits / umi_bits are the agreed fields
+		std::vector<u32> begin, count;           // [F] rows of every column
+	};
+	void gather_place_keys(const u64 *k, const u64 *vals, bool with_vals, u32 n_loc, int cell_shift, u32 F, const std::string &what, const char *gather_phase,
+	                       std::unique_ptr<Phase> &keys_phase, GlobalKeys &K);
+	void global_molecule_keys(GlobalKeys &K, bool with_above, const std::string &what, const char *keys_phase, const char *gather_phase);
 	void validation_global_view(dropest_ctx::ValidationView &V);
 	void run_merge_validation(const dropest_validation_opts *opts, dropest_validation_sample *samples, u32 n_samples);
 	bool keep_validation_keys = false;                            // option "keep_validation_keys" (test hook): the view keys of the last validation, on the host
 	std::vector<u64> val_keys_local, val_keys_placed;
+	// per-read corrected barcode and UMI over this shard's resident range (shard_read_corrections.h); COLLECTIVE
+	struct ReadCorrections {
+		bool valid = false;
+		uint64_t n = 0;
+		dropest::DevBuf<uint8_t> verdict; dropest::DevBuf<u32> column; dropest::DevBuf<u64> umi;
+		uint64_t counts[5] = {0, 0, 0, 0, 0};
+		void drop() { valid = false; n = 0; }
+	} corrections;
+	dropest::DevBuf<u64> d_col_barcode; bool col_barcode_valid = false;   // cm's column barcodes on this shard's GPU (dropest_shard_filtered_barcodes_device)
+	void build_read_corrections();
 };
 
 dropest::OrdinalMap dropest_shard::ordinal_map() const {
@@ -946,6 +968,7 @@ void dropest_shard::merge_umi_distribution() {
 #include "shard_merge_free.h"
 #include "shard_matrix.h"
 #include "shard_validation.h"
+#include "shard_read_corrections.h"
 
 // 7. global view of the real cells: every shard's rows, all-gathered; first_global = the stream ordinal of the cell's first read
 void dropest_shard::build_global_table() {
@@ -987,6 +1010,7 @@ void dropest_shard::step() {
 	dropest_ctx &c = *ctx;
 	HIP_CHECK(hipSetDevice(c.cfg.device));
 	stepped = false;   // (a step that fails part way leaves nothing the validation statistics may read)
+	corrections.drop(); col_barcode_valid = false;
 	Phase whole(this, "step");
 	// the ordinal ranges of all shards (ordinals name reads across shards: first-seen order, N-UMI tie breaks)
 	if (pushed.n) {   // reads pushed from host memory: wait for the last batch, use the store in place
@@ -1270,6 +1294,7 @@ dropest_status dropest_ctx_split(dropest_ctx *ctx, int32_t parts, dropest_shard 
 			dropest_shard &s = *made.back();
 			s.tr.reset(new dropest::LocalTransport(hub, i));
 			s.ctx->side = ctx->side;
+			s.ctx->save_umi_targets = ctx->save_umi_targets;   // Gene::merge_targets() are kept by the shards when the parent kept them
 			const uint64_t a = n * uint64_t(i) / uint64_t(parts), b = n * uint64_t(i + 1) / uint64_t(parts);
 			s.r_cb = ctx->d_cb + a; s.r_umi = ctx->d_umi + a; s.r_gene = ctx->d_gene + a; s.r_aux = ctx->d_aux + a;
 			s.n_res = b - a; s.first_ordinal = a;
@@ -1310,6 +1335,7 @@ dropest_status dropest_shard_set_reads_device(dropest_shard *s, const uint64_t *
 		if (n >= 0xFFFFFFFEull) throw UnsupportedError("more than 2^32-2 reads per shard");
 		s->r_cb = reinterpret_cast<const dropest::u64 *>(d_cb); s->r_umi = reinterpret_cast<const dropest::u64 *>(d_umi);
 		s->r_gene = d_gene; s->r_aux = d_aux; s->n_res = n; s->first_ordinal = first_ordinal;
+		s->corrections.drop();
 		s->pushed.clear();
 	});
 }

@@ -10,6 +10,8 @@
 //             shard -- the price of a replicated view.
 //   place     the gathered buffer is `world` sorted blocks and a cell's rows lie in exactly one: validation_place_kernel copies every cell's
 //             segment to its place in the global order.  No sort of the union.
+//             keys / gather / place are global_molecule_keys + gather_place_keys below: the read corrections of a sharded run
+//             (shard_read_corrections.h) take the same sorted array and the rows of every column from them.
 //   onwards   dropest_ctx::validation_finish_view: the (cell, gene) rows, the cells' ranges, the Poisson tables -- the one context's code.
 //   sampler   dropest_ctx::validation_sample on the global barcode rows, on every shard: the same GlibcRand(42), the same pairs, no collective
 //             inside the rounds.  cell1 / cell2 are COLUMNS OF THE FILTERED MATRIX.
@@ -21,23 +23,103 @@
 
 struct ValidationAgreed { int gene_bits = 0, umi_bits = 0; bool any_rows = false; std::vector<dropest::u64> above; };
 
-void dropest_shard::validation_global_view(dropest_ctx::ValidationView &V) {
+// `k`: this shard's n_loc keys column | ..., sorted, the column above bit cell_shift (every key's column is one of this shard's own cells);
+// with_vals (the same on every shard): one u64 of `vals` travels beside every key.  COLLECTIVE.  K.key / K.val: the keys (values) of all shards placed in global order, K.n of
+// them, K.begin / K.count the rows of every column.  `keys_phase` is closed once the local rows are counted.
+void dropest_shard::gather_place_keys(const u64 *k, const u64 *vals, bool with_vals, u32 n_loc, int cell_shift, u32 F, const std::string &what, const char *gather_phase,
+                                      std::unique_ptr<Phase> &keys_phase, GlobalKeys &K) {
 	using namespace dropest;
 	dropest_ctx &c = *ctx;
-	const auto t0 = std::chrono::steady_clock::now();
 	const Mat &M = mat[0];
-	if (M.col_row.size() != M.ncols) throw DeviceError("internal: the filtered matrix has no column table");
-	const u32 F = V.F = u32(M.ncols);
-	V.n_mol = V.n_cg = 0;
-	V.cells.resize(F); V.umis.resize(F);
-	for (u32 j = 0; j < F; ++j) { V.cells[j] = j; V.umis[j] = u32(G[M.col_row[j]].total_umis); }   // Cell::umis_number() = the TOTAL_UMIS stat
-	if (F < 2) return;
-	{
-		std::vector<std::string> text(F);
-		for (u32 j = 0; j < F; ++j) text[j] = decode_code(G[M.col_row[j]].barcode, c.side);   // (every shard has the whole side-string table)
-		c.validation_set_barcodes(V, text);
+	// rows per position: mine from the sorted keys, everybody's through the host, scanned
+	struct CellCount { u32 col, count; };
+	std::vector<CellCount> mine, every;
+	if (n_loc) {
+		DevBuf<u32> seg; seg.alloc(size_t(F) * 2);
+		HIP_CHECK(hipMemsetAsync(seg.p, 0, size_t(F) * 8, c.stream));
+		hipLaunchKernelGGL(validation_cell_segments_kernel, dim3(div_up(n_loc, 256)), dim3(256), 0, c.stream, k, n_loc, cell_shift, F, seg.p, seg.p + F);
+		HIP_CHECK(hipGetLastError());
+		std::vector<u32> h(size_t(F) * 2);
+		c.fetch(h.data(), seg.p, size_t(F) * 8);
+		uint64_t sum = 0;
+		for (u32 j = 0; j < F; ++j)
+			if (h[size_t(F) + j] > h[j]) {
+				if (h[j] != sum) throw DeviceError("internal: a shard's view keys do not lie cell by cell");
+				mine.push_back({j, h[size_t(F) + j] - h[j]}); sum += mine.back().count;
+			}
+		if (sum != n_loc) throw DeviceError("internal: a shard's view keys do not add up to its cells");
 	}
-	std::unique_ptr<Phase> ph_keys(new Phase(this, "validation:keys"));
+	if (keep_validation_keys && !with_vals) { val_keys_local.resize(n_loc); if (n_loc) c.fetch(val_keys_local.data(), k, size_t(n_loc) * 8); }
+	std::vector<size_t> cells_of;
+	keys_phase.reset();
+	Phase ph_gather(this, gather_phase);
+	tr->gather_vec(mine, every, cells_of);
+	std::vector<u32> cell_src(F, 0), &cell_cnt = K.count, &cell_dst = K.begin;
+	cell_cnt.assign(F, 0); cell_dst.assign(F, 0);
+	std::vector<size_t> off(static_cast<size_t>(world)), bytes(static_cast<size_t>(world));
+	uint64_t N = 0;
+	{
+		size_t at = 0;
+		for (int p = 0; p < world; ++p) {
+			off[size_t(p)] = size_t(N) * 8;
+			uint64_t run = N;
+			for (size_t i = 0; i < cells_of[size_t(p)]; ++i, ++at) {
+				const CellCount &cc = every[at];
+				if (cc.col >= F || cell_cnt[cc.col] || int(G[M.col_row[cc.col]].rank) != p) throw InvalidError("internal: two shards claim rows of one filtered cell");
+				if (run + cc.count >= 0xFFFFFFF0ull) throw UnsupportedError(what + ": too many molecules");
+				cell_src[cc.col] = u32(run); cell_cnt[cc.col] = cc.count;
+				run += cc.count;
+			}
+			bytes[size_t(p)] = size_t(run - N) * 8;
+			N = run;
+		}
+	}
+	if (size_t(n_loc) * 8 != bytes[size_t(rank)]) throw DeviceError("internal: the gathered row counts differ from this shard's rows");
+	K.n = 0;
+	if (!N) return;
+	std::vector<u32> piece_cell, piece_first;
+	{
+		u32 run = 0;
+		for (u32 j = 0; j < F; ++j) {
+			cell_dst[j] = run; run += cell_cnt[j];
+			for (u32 f = 0; f < cell_cnt[j]; f += VAL_SEG) { piece_cell.push_back(j); piece_first.push_back(f); }
+		}
+	}
+	DevBuf<u64> gathered; gathered.alloc(size_t(N));
+	const u32 n_pieces = u32(piece_cell.size());
+	DevBuf<u32> d_cells, d_pieces; d_cells.alloc(size_t(F) * 3); d_pieces.alloc(size_t(n_pieces) * 2);
+	c.upload(d_cells.p, cell_src.data(), size_t(F) * 4);
+	c.upload(d_cells.p + F, cell_cnt.data(), size_t(F) * 4);
+	c.upload(d_cells.p + 2 * size_t(F), cell_dst.data(), size_t(F) * 4);
+	c.upload(d_pieces.p, piece_cell.data(), size_t(n_pieces) * 4);
+	c.upload(d_pieces.p + n_pieces, piece_first.data(), size_t(n_pieces) * 4);
+	DevBuf<u64> dummy; dummy.alloc(1);
+	for (int pass = 0; pass < (with_vals ? 2 : 1); ++pass) {
+		const u64 *src = pass ? vals : k;
+		DevBuf<u64> &dst = pass ? K.val : K.key;
+		tr->gather_dev(src ? src : dummy.p, gathered.p, off.data(), bytes.data(), c.stream);
+		phases[gather_phase].bytes += double(N - n_loc) * 8;
+		dst.alloc(size_t(N) + 1);
+		c.timed("validation_place", double(N) * 16, [&] {
+			hipLaunchKernelGGL(validation_place_kernel, dim3(std::min<u32>(n_pieces, 2048)), dim3(256), 0, c.stream, gathered.p, dst.p, d_cells.p, d_cells.p + F,
+			                   d_cells.p + 2 * size_t(F), d_pieces.p, d_pieces.p + n_pieces, n_pieces);
+		});
+		HIP_CHECK(hipGetLastError());
+		HIP_CHECK(stream_wait(c.stream));   // (the tables of the launch leave this scope; `gathered` is written again)
+	}
+	K.n = u32(N);
+}
+
+// The molecules of ALL filtered cells under keys column of cm | gene | UMI field, sorted, on this shard (header comment: keys, gather, place).
+// COLLECTIVE.  with_above: override UMIs the field cannot hold get codes above it (merge validation counts them); without, they are left
+// out (no read carries one: the read corrections).  `what` starts the refusals' messages.
+void dropest_shard::global_molecule_keys(GlobalKeys &K, bool with_above, const std::string &what, const char *keys_phase, const char *gather_phase) {
+	using namespace dropest;
+	dropest_ctx &c = *ctx;
+	const Mat &M = mat[0];
+	const u32 F = K.F = u32(M.ncols);
+	K.n = 0; K.any_rows = false;
+	std::unique_ptr<Phase> ph_keys(new Phase(this, keys_phase));
 	const KeyLayout &L = c.layout;
 	const u32 nm = c.initialized ? c.n_mol : 0;
 	// my cells' positions; rewritten groups of my filtered cells: their keys for the device to skip, their rows under view keys
@@ -62,6 +144,7 @@ void dropest_shard::validation_global_view(dropest_ctx::ValidationView &V) {
 			for (const UmiOverride &o : kv.second) {
 				u64 field = 0;
 				const bool in_field = c.map_umi(o.umi, field);
+				if (!in_field && !with_above) continue;
 				if (!in_field) above_mine.push_back(o.umi);
 				orows.push_back({(u64(pos[cell]) << L.gene_bits) | (kv.first & L.gene_none), in_field ? field : o.umi, !in_field});
 			}
@@ -93,20 +176,21 @@ void dropest_shard::validation_global_view(dropest_ctx::ValidationView &V) {
 		std::sort(A.above.begin(), A.above.end());
 		A.above.erase(std::unique(A.above.begin(), A.above.end()), A.above.end());
 	}
-	if (too_many) throw UnsupportedError("merge validation: too many molecules");
-	if (!A.any_rows) { V.ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); return; }
+	if (too_many) throw UnsupportedError(what + ": too many molecules");
+	if (!A.any_rows) return;
+	K.any_rows = true;
 	const u64 umask = A.umi_bits ? ((1ull << A.umi_bits) - 1ull) : 0ull;
-	V.gene_bits = A.gene_bits; V.gene_none = (1ull << A.gene_bits) - 1ull;
-	V.umi_bits = A.umi_bits + (A.above.empty() ? 0 : 1);
-	if (u64(A.above.size()) > umask + 1) throw UnsupportedError("merge validation: more rewritten UMIs outside the UMI field than one more bit holds");
-	const int rank_bits = std::max(1, bit_length(uint64_t(F - 1)));
-	const int total_bits = rank_bits + A.gene_bits + V.umi_bits;
-	if (total_bits > 64) throw UnsupportedError("merge validation: the view's key (cell rank, gene, UMI) is wider than 64 bits");
+	K.gene_bits = A.gene_bits;
+	K.umi_bits = A.umi_bits + (A.above.empty() ? 0 : 1);
+	if (u64(A.above.size()) > umask + 1) throw UnsupportedError(what + ": more rewritten UMIs outside the UMI field than one more bit holds");
+	const int rank_bits = std::max(1, bit_length(uint64_t(F ? F - 1 : 0)));
+	const int total_bits = rank_bits + A.gene_bits + K.umi_bits;
+	if (total_bits > 64) throw UnsupportedError(what + ": the view's key (cell rank, gene, UMI) is wider than 64 bits");
 	std::vector<u64> extra;
 	extra.reserve(orows.size());
 	for (const Row &r : orows) {
 		const u64 code = r.above ? umask + 1 + u64(std::lower_bound(A.above.begin(), A.above.end(), r.umi) - A.above.begin()) : r.umi;
-		extra.push_back((r.cg << V.umi_bits) | code);
+		extra.push_back((r.cg << K.umi_bits) | code);
 	}
 
 	// my rows under view keys, sorted
@@ -123,7 +207,7 @@ void dropest_shard::validation_global_view(dropest_ctx::ValidationView &V) {
 			c.scalars.ensure(16);
 			HIP_CHECK(hipMemsetAsync(c.scalars.p, 0, 16, c.stream));
 			hipLaunchKernelGGL(validation_view_keys_kernel, dim3(div_up(nm, 256)), dim3(256), 0, c.stream, c.mol_key.p, nm, L.umi_bits, L.gene_bits, L.gene_none,
-			                   V.umi_bits, c.remap.p, d_rewritten.p, u32(rewritten.size()), c.keys_a.p, c.scalars.p);
+			                   K.umi_bits, c.remap.p, d_rewritten.p, u32(rewritten.size()), c.keys_a.p, c.scalars.p);
 			HIP_CHECK(hipGetLastError());
 			c.fetch(&kept, c.scalars.p, 4);
 		}
@@ -133,81 +217,32 @@ void dropest_shard::validation_global_view(dropest_ctx::ValidationView &V) {
 	u64 *k = c.keys_a.p, *k_alt = c.keys_b.p;
 	u32 *v = c.vals_a.p, *v_alt = c.vals_b.p;
 	if (n_loc) c.radix_sort(k, v, k_alt, v_alt, n_loc, total_bits >= 64 ? ~0ull : ((1ull << total_bits) - 1ull));
+	gather_place_keys(k, nullptr, false, n_loc, A.gene_bits + K.umi_bits, F, what, gather_phase, ph_keys, K);
+}
 
-	// rows per position: mine from the sorted keys, everybody's through the host, scanned
-	struct CellCount { u32 col, count; };
-	std::vector<CellCount> mine, every;
-	if (n_loc) {
-		DevBuf<u32> seg; seg.alloc(size_t(F) * 2);
-		HIP_CHECK(hipMemsetAsync(seg.p, 0, size_t(F) * 8, c.stream));
-		hipLaunchKernelGGL(validation_cell_segments_kernel, dim3(div_up(n_loc, 256)), dim3(256), 0, c.stream, k, n_loc, A.gene_bits + V.umi_bits, F, seg.p, seg.p + F);
-		HIP_CHECK(hipGetLastError());
-		std::vector<u32> h(size_t(F) * 2);
-		c.fetch(h.data(), seg.p, size_t(F) * 8);
-		uint64_t sum = 0;
-		for (u32 j = 0; j < F; ++j)
-			if (h[size_t(F) + j] > h[j]) {
-				if (h[j] != sum) throw DeviceError("internal: a shard's view keys do not lie cell by cell");
-				mine.push_back({j, h[size_t(F) + j] - h[j]}); sum += mine.back().count;
-			}
-		if (sum != n_loc) throw DeviceError("internal: a shard's view keys do not add up to its cells");
-	}
-	if (keep_validation_keys) { val_keys_local.resize(n_loc); if (n_loc) c.fetch(val_keys_local.data(), k, size_t(n_loc) * 8); }
-	std::vector<size_t> cells_of;
-	ph_keys.reset();
-	std::unique_ptr<Phase> ph_gather(new Phase(this, "validation:gather_place"));
-	tr->gather_vec(mine, every, cells_of);
-	std::vector<u32> cell_src(F, 0), cell_cnt(F, 0), cell_dst(F, 0);
-	std::vector<size_t> off(static_cast<size_t>(world)), bytes(static_cast<size_t>(world));
-	uint64_t N = 0;
+void dropest_shard::validation_global_view(dropest_ctx::ValidationView &V) {
+	using namespace dropest;
+	dropest_ctx &c = *ctx;
+	const auto t0 = std::chrono::steady_clock::now();
+	const Mat &M = mat[0];
+	if (M.col_row.size() != M.ncols) throw DeviceError("internal: the filtered matrix has no column table");
+	const u32 F = V.F = u32(M.ncols);
+	V.n_mol = V.n_cg = 0;
+	V.cells.resize(F); V.umis.resize(F);
+	for (u32 j = 0; j < F; ++j) { V.cells[j] = j; V.umis[j] = u32(G[M.col_row[j]].total_umis); }   // Cell::umis_number() = the TOTAL_UMIS stat
+	if (F < 2) return;
 	{
-		size_t at = 0;
-		for (int p = 0; p < world; ++p) {
-			off[size_t(p)] = size_t(N) * 8;
-			uint64_t run = N;
-			for (size_t i = 0; i < cells_of[size_t(p)]; ++i, ++at) {
-				const CellCount &cc = every[at];
-				if (cc.col >= F || cell_cnt[cc.col] || int(G[M.col_row[cc.col]].rank) != p) throw InvalidError("internal: two shards claim rows of one filtered cell");
-				if (run + cc.count >= 0xFFFFFFF0ull) throw UnsupportedError("merge validation: too many molecules");
-				cell_src[cc.col] = u32(run); cell_cnt[cc.col] = cc.count;
-				run += cc.count;
-			}
-			bytes[size_t(p)] = size_t(run - N) * 8;
-			N = run;
-		}
+		std::vector<std::string> text(F);
+		for (u32 j = 0; j < F; ++j) text[j] = decode_code(G[M.col_row[j]].barcode, c.side);   // (every shard has the whole side-string table)
+		c.validation_set_barcodes(V, text);
 	}
-	if (size_t(n_loc) * 8 != bytes[size_t(rank)]) throw DeviceError("internal: the gathered row counts differ from this shard's rows");
-	if (!N) { V.ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); return; }
-	std::vector<u32> piece_cell, piece_first;
-	{
-		u32 run = 0;
-		for (u32 j = 0; j < F; ++j) {
-			cell_dst[j] = run; run += cell_cnt[j];
-			for (u32 f = 0; f < cell_cnt[j]; f += VAL_SEG) { piece_cell.push_back(j); piece_first.push_back(f); }
-		}
-	}
-	DevBuf<u64> gathered; gathered.alloc(size_t(N));
-	tr->gather_dev(k, gathered.p, off.data(), bytes.data(), c.stream);
-	phases["validation:gather_place"].bytes += double(N - n_loc) * 8;
-	{
-		const u32 n_pieces = u32(piece_cell.size());
-		DevBuf<u32> d_cells, d_pieces; d_cells.alloc(size_t(F) * 3); d_pieces.alloc(size_t(n_pieces) * 2);
-		c.upload(d_cells.p, cell_src.data(), size_t(F) * 4);
-		c.upload(d_cells.p + F, cell_cnt.data(), size_t(F) * 4);
-		c.upload(d_cells.p + 2 * size_t(F), cell_dst.data(), size_t(F) * 4);
-		c.upload(d_pieces.p, piece_cell.data(), size_t(n_pieces) * 4);
-		c.upload(d_pieces.p + n_pieces, piece_first.data(), size_t(n_pieces) * 4);
-		V.mol_key.alloc(size_t(N) + 1);
-		c.timed("validation_place", double(N) * 16, [&] {
-			hipLaunchKernelGGL(validation_place_kernel, dim3(std::min<u32>(n_pieces, 2048)), dim3(256), 0, c.stream, gathered.p, V.mol_key.p, d_cells.p, d_cells.p + F,
-			                   d_cells.p + 2 * size_t(F), d_pieces.p, d_pieces.p + n_pieces, n_pieces);
-		});
-		HIP_CHECK(hipGetLastError());
-		HIP_CHECK(stream_wait(c.stream));   // (the tables of the launch leave this scope)
-	}
-	ph_gather.reset();
-	V.n_mol = u32(N);
-	if (keep_validation_keys) { val_keys_placed.resize(size_t(N)); c.fetch(val_keys_placed.data(), V.mol_key.p, size_t(N) * 8); }
+	GlobalKeys K;
+	global_molecule_keys(K, true, "merge validation", "validation:keys", "validation:gather_place");
+	if (K.any_rows) { V.gene_bits = K.gene_bits; V.gene_none = (1ull << K.gene_bits) - 1ull; V.umi_bits = K.umi_bits; }
+	if (!K.n) { V.ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); return; }
+	V.mol_key = std::move(K.key);
+	V.n_mol = K.n;
+	if (keep_validation_keys) { val_keys_placed.resize(size_t(K.n)); c.fetch(val_keys_placed.data(), V.mol_key.p, size_t(K.n) * 8); }
 	{ Phase ph_rows(this, "validation:rows_tables"); c.validation_finish_view(V); }
 	V.ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }

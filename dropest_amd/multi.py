@@ -97,6 +97,20 @@ class Shard:
         self._chk(self.L.dropest_shard_merge_validation_samples(self.h, C.byref(opts), S, len(samples)))
         return capi.validation_results(samples, single, S, arrays)
 
+    def read_corrections_device(self):
+        """(n, first_ordinal, d_verdict, d_column, d_umi) over this shard's resident range: raw device pointers on its GPU, valid until
+        its next step (dropest_shard_read_corrections).  COLLECTIVE unless the group computed them since the last step."""
+        n, first = C.c_uint64(), C.c_uint64()
+        pv, pc, pu = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        self._chk(self.L.dropest_shard_read_corrections(self.h, C.byref(n), C.byref(first), C.byref(pv), C.byref(pc), C.byref(pu)))
+        return n.value, first.value, pv.value, pc.value, pu.value
+
+    def filtered_barcodes_device(self):
+        """(n, d_codes): the barcode code of every column of the filtered matrix, a raw device pointer on this shard's GPU."""
+        n, p = C.c_uint64(), C.c_void_p()
+        self._chk(self.L.dropest_shard_filtered_barcodes_device(self.h, C.byref(n), C.byref(p)))
+        return n.value, p.value
+
     def matrix(self, filtered):
         """(colptr u64[ncols + 1], rowidx u32[nnz], values u32[nnz], column barcodes u64[ncols]) of the GLOBAL matrix: views of
         library-owned memory, valid until the next step (meaningful on shard 0)."""
@@ -237,6 +251,32 @@ class ShardGroup:
         if rc != 0:
             raise capi.DropestError(rc, self.L.dropest_last_error().decode())
         return capi.validation_results(samples, single, S, arrays)
+
+    def _n_reads(self):
+        return sum(s.read_corrections_device()[0] for s in self.shards)
+
+    def read_corrections(self, first=0, count=None):
+        """Host copies (verdict u8, column of the filtered matrix u32, corrected UMI u64) of reads [first, first + count) of the WHOLE
+        stream, assembled across the shards' ranges (dropest_shard_group_read_corrections_host); matrix(True)[3] names the columns."""
+        rc = self.L.dropest_shard_group_read_corrections(self._handles, len(self.shards))
+        if rc != 0:
+            raise capi.DropestError(rc, self.L.dropest_last_error().decode())
+        if count is None:
+            count = self._n_reads() - first
+        verdict = np.zeros(count, np.uint8); column = np.zeros(count, np.uint32); umi = np.zeros(count, np.uint64)
+        rc = self.L.dropest_shard_group_read_corrections_host(self._handles, len(self.shards), first, count, verdict.ctypes.data, column.ctypes.data,
+                                                              umi.ctypes.data)
+        if rc != 0:
+            raise capi.DropestError(rc, self.L.dropest_last_error().decode())
+        return verdict, column, umi
+
+    def read_correction_counts(self):
+        """Reads per verdict over all shards: [written, no gene, cell not kept, wrong gene, wrong UMI]."""
+        out = np.zeros(5, np.uint64)
+        rc = self.L.dropest_shard_group_read_correction_counts(self._handles, len(self.shards), out.ctypes.data)
+        if rc != 0:
+            raise capi.DropestError(rc, self.L.dropest_last_error().decode())
+        return out
 
     def close(self):
         for s in self.shards:

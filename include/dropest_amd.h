@@ -211,7 +211,8 @@ dropest_status dropest_umi_merge_targets(dropest_ctx *ctx, uint64_t *n, uint32_t
  *            looked up among the molecules, and before the next test, :79-83), else the read's own UMI, which is then a molecule of the
  *            gene (:84-87); any other verdict: the read's own UMI.  Packed / escaped as on the way in.
  * With save_umi_merge_targets off the reads of merged-away UMIs get verdict 4, as in the reference.  Refused (DROPEST_ERR_UNSUPPORTED): a
- * shard's context, a context dropest_ctx_split emptied, a pass in UMI-dictionary mode (dropest_set_umi_dictionary).
+ * shard's context and a context dropest_ctx_split emptied (dropest_shard_read_corrections / dropest_shard_group_read_corrections answer for
+ * those), a pass in UMI-dictionary mode (dropest_set_umi_dictionary).
  * dropest_read_corrections_host copies entries [first, first + count) to host arrays (any may be null);
  * dropest_read_correction_counts gives the number of reads per verdict (out[0] = _written_reads, out[3] = _wrong_genes, out[4] = _wrong_umis). */
 dropest_status dropest_read_corrections(dropest_ctx *ctx, uint64_t *n, const uint8_t **d_verdict, const uint32_t **d_cell,
@@ -686,6 +687,33 @@ dropest_status dropest_shard_merge_validation_samples(dropest_shard *shard, cons
  * dropest_shard_group_step; the caller's arrays are filled once, from shard 0. */
 dropest_status dropest_shard_group_merge_validation_samples(dropest_shard *const *shards, int32_t n, const dropest_validation_opts *opts,
                                                             dropest_validation_sample *samples, uint32_t n_samples);
+/* dropest_read_corrections (`dropest -F`, the decisions) for the shards of a sharded or split run.  COLLECTIVE: every shard of the run calls it
+ * after a step (before one: DROPEST_ERR_INVALID, "You must initialize container").  Three DEVICE arrays on the shard's GPU over ITS RESIDENT
+ * RANGE of the stream -- *n reads from stream ordinal *first_ordinal on, in stream order -- owned by the shard and valid until its next step,
+ * new reads or destroy (any output pointer may be null):
+ *   verdict  as dropest_read_corrections
+ *   column   the COLUMN OF THE FILTERED MATRIX of the target cell (verdicts 0, 3, 4; 0xFFFFFFFF for 1 and 2): the shards number their cells
+ *            separately.  dropest_shard_filtered_barcodes_device names the columns.
+ *   umi      as dropest_read_corrections
+ * Gene::merge_targets() are kept when dropest_set_save_umi_merge_targets was set on dropest_shard_ctx(shard) of EVERY shard before the step
+ * (dropest_ctx_split carries the parent's setting into its shards).
+ * The call is cached: a repeat without a new step does no work and enters no collective.  Every shard builds the same table barcode -> column
+ * (16 bytes x a power of two of at least twice the kept and merged cells) and the same view of all filtered cells' molecules (8 bytes per
+ * molecule on every GPU, as the merge validation pays).  Refused by ALL shards alike, leaving the run usable: UMI-dictionary mode
+ * (DROPEST_ERR_UNSUPPORTED), a key (column, gene, UMI) wider than 64 bits, 2^32 - 16 or more molecules in the view. */
+dropest_status dropest_shard_read_corrections(dropest_shard *shard, uint64_t *n, uint64_t *first_ordinal, const uint8_t **d_verdict,
+                                              const uint32_t **d_column, const uint64_t **d_umi);
+/* The same for the shards of one process: one host thread per shard, errors as in dropest_shard_group_step. */
+dropest_status dropest_shard_group_read_corrections(dropest_shard *const *shards, int32_t n);
+/* Entries [first, first + count) of the WHOLE stream -- the shards' resident ranges one behind the other -- copied to host arrays (any may be
+ * null); the reads per verdict summed over the shards.  Both compute the corrections first when a step has passed since. */
+dropest_status dropest_shard_group_read_corrections_host(dropest_shard *const *shards, int32_t n, uint64_t first, uint64_t count, uint8_t *verdict,
+                                                         uint32_t *column, uint64_t *umi);
+dropest_status dropest_shard_group_read_correction_counts(dropest_shard *const *shards, int32_t n, uint64_t out[5]);
+/* The barcode of every column of the filtered matrix in the packed / escaped form of the way in: a DEVICE array of *n codes on the shard's
+ * GPU, owned by the shard and valid until its next step -- what a `column` entry stands for, in the form dropest_bam_filter_cfg::cell_barcode
+ * takes.  Not collective. */
+dropest_status dropest_shard_filtered_barcodes_device(dropest_shard *shard, uint64_t *n, const uint64_t **d_codes);
 /* How the pairs of one sample are dealt to the shards for evaluation: cnt[p] = common genes of pair p; shard r takes pairs
  * [bounds[r], bounds[r + 1]), bounds[0] = 0, bounds[world] = n_pairs.  Range r ends behind the first pair at which the running sum of cnt
  * reaches (r + 1) * total / world; pairs with cnt = 0 ride along; total = 0: equal numbers of pairs.  Plain host code (no device). */
