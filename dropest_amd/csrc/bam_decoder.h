@@ -166,7 +166,8 @@ struct BamTagging {
 	uint64_t bytes_in = 0, bytes_out = 0;
 	// -F (dropest_bam_decoder_set_filtering / _filter_window): the two corrected tags' names, every cell's barcode code (the caller's device array,
 	// or `codes`, a copy of its host array), the side strings of escaped codes, each record's rank among the accepted ones, and a window's
-	// decisions when they come from host arrays (through h_fix, pinned)
+	// decisions when they come from host arrays (through h_fix, pinned).  _filter_window_segments: the segment table (through h_seg, pinned, to
+	// `seg`); umi / cell / verdict are then the staging of segments whose arrays live on another GPU (or of all, under the test switch)
 	struct Filtering {
 		bool on = false;
 		uint32_t out_tag[2] = {0, 0}, n_cells = 0, n_side = 0;
@@ -174,7 +175,9 @@ struct BamTagging {
 		DevBuf<uint64_t> codes, umi;
 		DevBuf<uint32_t> side_off, rank, tile_ok, total, cell;
 		DevBuf<uint8_t> side_pool, verdict;
+		DevBuf<BamTagSeg> seg;
 		PinnedBuf<uint64_t> h_fix;
+		PinnedBuf<BamTagSeg> h_seg;
 	} filt;
 	void reset() { on = false; has_names = false; pending = false; len = 0; ms = 0; bytes_in = bytes_out = 0; filt.on = false; }      // (the names were the annotation's)
 };

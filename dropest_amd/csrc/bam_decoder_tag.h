@@ -1,5 +1,6 @@
 // bam_decoder_tag.h -- -b and -F: the accepted records of the LAST finished window with their tags edited; under -F only those the container's
-// decision writes, with the corrected barcode and UMI behind the other tags (k_bamtag.h; the state: BamTagging, bam_decoder.h)
+// decision writes, with the corrected barcode and UMI behind the other tags (k_bamtag.h; the state: BamTagging, bam_decoder.h).  The decisions come
+// as one array (_filter_window: one context's) or in segments (_filter_window_segments: the shards' of a sharded run, one table entry each)
 #pragma once
 
 extern "C" int dropest_bam_decoder_set_tagging(dropest_bam_decoder *d, const dropest_bam_tag_cfg *cfg) {
@@ -72,8 +73,8 @@ static BamTagIn tag_in(dropest_bam_decoder *d) {
 }
 
 // each record's output size, the tiles' sums and every record's place; the wait for the one total that sizes the output (in h_tag)
-// (filt: -F -- every record's rank among the accepted ones first, the sizes by the decisions)
-static void tag_plan(dropest_bam_decoder *d, hipStream_t st, const BamTagIn &in, const BamTagNames &names, uint32_t grid, uint32_t tiles, const BamTagFilt *filt) {
+// (filt: -F -- every record's rank among the accepted ones first, the sizes by the decisions; segs: the decisions stand in segments)
+static void tag_plan(dropest_bam_decoder *d, hipStream_t st, const BamTagIn &in, const BamTagNames &names, uint32_t grid, uint32_t tiles, const BamTagFilt *filt, const BamTagSegments *segs) {
 	BamTagging &T = d->tag;
 	const uint32_t n_rec = in.n_rec;
 	HIP_CHECK(hipMemsetAsync(T.flags.p, 0, 4, st));
@@ -82,7 +83,8 @@ static void tag_plan(dropest_bam_decoder *d, hipStream_t st, const BamTagIn &in,
 		hipLaunchKernelGGL(bam_tag_rank_tile_kernel, dim3(tiles), dim3(256), 0, st, in.status, n_rec, T.filt.tile_ok.p);
 		hipLaunchKernelGGL(bam_tag_rank_scan_kernel, dim3(1), dim3(1024), 0, st, T.filt.tile_ok.p, tiles, T.filt.total.p);
 		hipLaunchKernelGGL(bam_tag_rank_kernel, dim3(tiles), dim3(256), 0, st, in.status, n_rec, T.filt.tile_ok.p, T.filt.rank.p);
-		hipLaunchKernelGGL(bam_tag_filter_plan_kernel, dim3(grid), dim3(BAMTAG_T), 0, st, in, d->cfg, T.cfg, names, *filt, T.size.p, T.flags.p);
+		if (segs) hipLaunchKernelGGL(bam_tag_filter_plan_kernel<BamTagSegments>, dim3(grid), dim3(BAMTAG_T), 0, st, in, d->cfg, T.cfg, names, *filt, T.size.p, T.flags.p, *segs);
+		else hipLaunchKernelGGL(bam_tag_filter_plan_kernel<BamTagOneArray>, dim3(grid), dim3(BAMTAG_T), 0, st, in, d->cfg, T.cfg, names, *filt, T.size.p, T.flags.p, BamTagOneArray{});
 	} else
 		hipLaunchKernelGGL(bam_tag_plan_kernel, dim3(grid), dim3(BAMTAG_T), 0, st, in, d->cfg, T.cfg, names, T.size.p, T.flags.p);
 	hipLaunchKernelGGL(bam_tag_tile_sum_kernel, dim3(tiles), dim3(256), 0, st, T.size.p, n_rec, T.tile_bytes.p, T.tile_written.p);
@@ -97,8 +99,9 @@ static void tag_plan(dropest_bam_decoder *d, hipStream_t st, const BamTagIn &in,
 	T.ms += ms_plan;
 }
 
-// What _tag_window and _filter_window share: plan, the one wait, emit.  filt: -F (its rank pointer and decisions are set by the caller).
-static void tag_run(dropest_bam_decoder *d, const BamTagFilt *filt, const uint8_t **d_out, uint64_t *len, uint64_t *n_written, bool &undecided) {
+// What _tag_window and _filter_window share: plan, the one wait, emit.  filt: -F (its rank pointer and decisions are set by the caller); segs:
+// the decisions stand in segments (_filter_window_segments: filt's own three arrays are not looked at).
+static void tag_run(dropest_bam_decoder *d, const BamTagFilt *filt, const uint8_t **d_out, uint64_t *len, uint64_t *n_written, bool &undecided, const BamTagSegments *segs = nullptr) {
 	BamTagging &T = d->tag;
 	const uint64_t n_rec = d->at.last_n_rec;
 	hipStream_t st = d->stream;
@@ -110,9 +113,9 @@ static void tag_run(dropest_bam_decoder *d, const BamTagFilt *filt, const uint8_
 	const BamTagIn in = tag_in(d);
 	const BamTagNames names{d->dict.annotation ? T.name_off.p : nullptr, T.name_pool.p, T.n_names};
 	const uint32_t grid = uint32_t((n_rec + BAMTAG_WAVES - 1) / BAMTAG_WAVES);
-	tag_plan(d, st, in, names, grid, tiles, filt);
+	tag_plan(d, st, in, names, grid, tiles, filt, segs);
 	const uint64_t total = T.h_tag.p[0], written = T.h_tag.p[1];
-	if (T.h_tag.p[2] & BAMTAG_FLAG_RANGE) throw RangeError("the decision of a read that is written names a cell or a side string that does not exist");
+	if (T.h_tag.p[2] & BAMTAG_FLAG_RANGE) throw RangeError("the decision of a read that is written names a cell or a side string that does not exist");      // (or no segment covers it: never, the counts were checked)
 	if (T.h_tag.p[2] & BAMTAG_FLAG_UNDECIDED) {
 		undecided = true;
 		throw UnsupportedError("the annotation query left the gene of some reads to the host: give their genes and marks with dropest_bam_decoder_patch_annotation and tag the window again");
@@ -122,7 +125,8 @@ static void tag_run(dropest_bam_decoder *d, const BamTagFilt *filt, const uint8_
 	if (filt && !total) return;                  // (-F: no read of this window is written)
 	T.out.ensure(size_t(total) + size_t(total) / 8 + 64);
 	HIP_CHECK(hipEventRecord(T.ev[2], st));      // (the kernels' time: the host's wait and the allocation between them are not theirs)
-	if (filt) hipLaunchKernelGGL(bam_tag_filter_emit_kernel, dim3(grid), dim3(BAMTAG_T), 0, st, in, d->cfg, T.cfg, names, *filt, T.size.p, T.off.p, T.out.p, total, T.flags.p);
+	if (filt && segs) hipLaunchKernelGGL(bam_tag_filter_emit_kernel<BamTagSegments>, dim3(grid), dim3(BAMTAG_T), 0, st, in, d->cfg, T.cfg, names, *filt, T.size.p, T.off.p, T.out.p, total, T.flags.p, *segs);
+	else if (filt) hipLaunchKernelGGL(bam_tag_filter_emit_kernel<BamTagOneArray>, dim3(grid), dim3(BAMTAG_T), 0, st, in, d->cfg, T.cfg, names, *filt, T.size.p, T.off.p, T.out.p, total, T.flags.p, BamTagOneArray{});
 	else hipLaunchKernelGGL(bam_tag_emit_kernel, dim3(grid), dim3(BAMTAG_T), 0, st, in, d->cfg, T.cfg, names, T.size.p, T.off.p, T.out.p, total, T.flags.p);
 	HIP_CHECK(hipGetLastError());
 	bam_copy(st, 1u, to_host(T.flags.p, reinterpret_cast<uint32_t *>(T.h_tag.p + 3)));
@@ -228,6 +232,71 @@ extern "C" int dropest_bam_decoder_filter_window(dropest_bam_decoder *d, const u
 		f.side_off = F.side_off.p; f.side_pool = F.side_pool.p; f.n_side = F.n_side;
 		f.out_tag[0] = F.out_tag[0]; f.out_tag[1] = F.out_tag[1];
 		tag_run(d, &f, d_out, len, n_written, undecided);
+	});
+	return rc && undecided ? 2 : rc;
+}
+
+// The decisions in segments (a sharded run: one segment per shard whose resident range meets the window).  Segments of the decoder's GPU are read
+// where they are; those of another GPU are copied into the decoder's staging first (hipMemcpyPeerAsync on the decoder's stream: the arrays are
+// finished when the caller has them -- dropest_shard_read_corrections waits for the owning shard's stream before it returns -- so the copy is
+// ordered behind that stream by the caller's own wait).  That copy has never run: no machine with two GPUs was there.
+// DROPEST_BAM_TEST_STAGE_SEGMENTS=1 (tests) sends every segment through the staging, so that all but the hop between two devices runs on one GPU.
+extern "C" int dropest_bam_decoder_filter_window_segments(dropest_bam_decoder *d, const dropest_bam_decision_segment *seg, uint32_t n_seg, const uint8_t **d_out, uint64_t *len,
+                                                          uint64_t *n_written) {
+	bool undecided = false;
+	const int rc = bgzf_guarded([&] {
+		if (!d || !d_out || !len || !n_written || (n_seg && !seg)) throw InvalidError("null argument");
+		*d_out = nullptr; *len = 0; *n_written = 0;
+		BamTagging &T = d->tag;
+		BamTagging::Filtering &F = T.filt;
+		if (!T.on) throw InvalidError("tagging is not configured for this decoder (dropest_bam_decoder_set_tagging)");
+		if (!F.on) throw InvalidError("filtering is not configured for this decoder (dropest_bam_decoder_set_filtering)");
+		if (d->dict.annotation && !T.has_names) throw InvalidError("with an annotation the tagging configuration must bring its gene names");
+		T.len = 0;
+		uint64_t n = 0;
+		bool wraps = false;
+		for (uint32_t s = 0; s < n_seg; ++s) { wraps |= seg[s].count > ~0ull - n; n += seg[s].count; }
+		if (wraps || n != d->at.last_n_ok) throw InvalidError(std::to_string(n) + " decisions for a window of " + std::to_string(d->at.last_n_ok) + " accepted records");
+		for (uint32_t s = 0; s < n_seg; ++s) if (seg[s].count && (!seg[s].verdict || !seg[s].cell || !seg[s].umi)) throw InvalidError("null argument");
+		const uint64_t n_rec = d->at.last_n_rec;
+		if (!n_rec) return;
+		HIP_CHECK(hipSetDevice(d->device));
+		bam_ready(d);
+		const uint32_t tiles = uint32_t((n_rec + BAMTAG_SCAN_TILE - 1) / BAMTAG_SCAN_TILE);
+		F.rank.ensure(size_t(n_rec) + size_t(n_rec) / 4); F.tile_ok.ensure(tiles + tiles / 4 + 1); F.total.ensure(1);
+		const char *const sw = getenv("DROPEST_BAM_TEST_STAGE_SEGMENTS");
+		const bool stage_all = sw && sw[0] == '1';
+		bool staged = false;
+		for (uint32_t s = 0; s < n_seg; ++s) staged |= seg[s].count && (stage_all || seg[s].device != d->device);
+		HIP_CHECK(hipStreamSynchronize(d->stream));      // (a call before this one that failed half-way may still be reading the table's staging)
+		if (staged) { const size_t m = size_t(n); F.umi.ensure(m + m / 4); F.cell.ensure(m + m / 4); F.verdict.ensure(m + m / 4); }
+		F.h_seg.ensure(size_t(n_seg) + 1); F.seg.ensure(size_t(n_seg) + size_t(n_seg) / 4 + 1);
+		uint32_t first = 0;
+		for (uint32_t s = 0; s < n_seg; ++s) {
+			const dropest_bam_decision_segment &g = seg[s];
+			const uint32_t count = uint32_t(g.count);      // (<= the window's records, which a 32-bit rank numbers)
+			BamTagSeg e{first, count, g.verdict, g.cell, g.umi};
+			if (count && (stage_all || g.device != d->device)) {
+				const void *const src[3] = {g.verdict, g.cell, g.umi};
+				void *const dst[3] = {F.verdict.p + first, F.cell.p + first, F.umi.p + first};
+				const size_t width[3] = {1, 4, 8};
+				for (int k = 0; k < 3; ++k) {
+					if (g.device != d->device) HIP_CHECK(hipMemcpyPeerAsync(dst[k], d->device, src[k], g.device, size_t(count) * width[k], d->stream));
+					else HIP_CHECK(hipMemcpyAsync(dst[k], src[k], size_t(count) * width[k], hipMemcpyDeviceToDevice, d->stream));
+				}
+				e.verdict = F.verdict.p + first; e.cell = F.cell.p + first; e.umi = F.umi.p + first;
+			}
+			F.h_seg.p[s] = e;
+			first += count;
+		}
+		bam_copy(d->stream, n_seg, from_host(static_cast<const BamTagSeg *>(F.h_seg.p), F.seg.p));
+		BamTagFilt f{};
+		f.rank = F.rank.p; f.n = uint32_t(n);
+		f.cell_barcode = F.cell_barcode; f.n_cells = F.n_cells;
+		f.side_off = F.side_off.p; f.side_pool = F.side_pool.p; f.n_side = F.n_side;
+		f.out_tag[0] = F.out_tag[0]; f.out_tag[1] = F.out_tag[1];
+		const BamTagSegments segs{F.seg.p, n_seg};
+		tag_run(d, &f, d_out, len, n_written, undecided, &segs);      // (waits for the stream before it returns: the table's staging is free again)
 	});
 	return rc && undecided ? 2 : rc;
 }

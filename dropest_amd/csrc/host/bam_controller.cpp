@@ -279,7 +279,7 @@ void BamController::write_filtered_bam_files(const std::vector<std::string> &bam
 	if (why) throw std::runtime_error(std::string("Filtered BAM output (-F) is written on the device BAM path only, which this configuration cannot take: ") + why);
 	if (bam_files.empty()) return;
 	join_release_thread();
-	FilteredPass *pass = filtered_pass_open(sw, container, _filtered);
+	FilteredPass *pass = filtered_pass_open(sw, container, _filtered, _sharded_filtered_output);
 	Counters second_pass;      // (the reads were counted when the container was filled)
 	try {
 		// did this controller fill the container?  Then file k brings what it brought then (a count guard per file: it sees files in another order)

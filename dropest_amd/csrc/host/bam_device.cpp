@@ -15,7 +15,10 @@
 // Filtered BAM output (-F: BamController::write_filtered_bam_files) is this path's second mode (FileIngest::filtered): the files are decoded again,
 // nothing goes into the container, every window's accepted records are edited by the tag kernels' filtered mode under the container's per-read
 // decisions (dropest_bam_decoder_filter_window; the decisions stay on the device) and ONE compressor stream writes the one output of the call
-// (FilteredPass, open_filtered, filter_window, close_filtered).
+// (FilteredPass, open_filtered, filter_window, close_filtered).  Over a sharded or split container (BamController::set_sharded_filtered_output; off:
+// refused) the decisions are the shards': FilteredPass holds every shard's range of the stream and its three device arrays, filter_window cuts
+// [at, at + n_accepted) at the ranges' boundaries and hands the pieces to dropest_bam_decoder_filter_window_segments, each file's decoder sits on
+// the GPU and stream of the shard that holds the file's first read, and the compressor follows the decoder from one stream to the next.
 // A sharded container is fed the same way: ONE decoder, on the GPU of the shard the file's first read goes to and on that shard's stream, for the
 // whole file (the record cut off at a window's end waits inside it); the container cuts every window at its quota boundaries and appends the
 // pieces to the shards' resident reads, device to device.
@@ -78,24 +81,78 @@ struct FilteredPass {
 	uint64_t n_reads = 0, n_cells = 0, at = 0, written = 0;      // at: accepted records of the files so far = the next window's first decision
 	uint64_t counts[5] = {0, 0, 0, 0, 0};
 	std::vector<uint32_t> side_off; std::vector<uint8_t> side_pool;      // the container's side strings as the decoder takes them
+	// The second shape, a sharded or split container (BamController::set_sharded_filtered_output): no array holds every read's decision --
+	// shard k holds those of reads [first, first + n) of the stream, the range it reports itself (dropest_shard_read_corrections after ONE
+	// dropest_shard_group_read_corrections over all shards), on its GPU; `column` plays the part of `cell`: it indexes the columns that
+	// dropest_shard_filtered_barcodes_device names (the same list on every shard; each file's decoder takes the copy of the shard it sits with).
+	struct Piece { dropest_shard *shard; int device; void *stream; uint64_t first, n; const uint8_t *verdict; const uint32_t *column; const uint64_t *umi; };
+	std::vector<Piece> pieces;
+	size_t cur = 0;                  // the shard the current file's decoder sits with: the one that holds the file's first read
 	std::string name;
 	std::FILE *f = nullptr;
 	dropest_deflate_stream *z = nullptr;
+	int z_device = -1; void *z_stream = nullptr;      // where the compressor runs: the decoder's GPU and stream
+	uint64_t z_in = 0, z_out = 0, z_batches = 0;      // what the compressors that are through took and gave
+	double z_ms = 0;
 	size_t windows = 0;
-	double decode_ms = 0, tag_ms = 0;
+	double decode_ms = 0, tag_ms = 0, decisions_ms = 0;
 	FilteredPass(const BamSwitches &sw, CellsDataContainer &container, BamController::FilteredFile &report) : sw(sw), container(container), report(report) {}
 	~FilteredPass() { if (z) dropest_deflate_stream_destroy(z); if (f) std::fclose(f); }
 	static int write(const uint8_t *bytes, uint64_t len, void *user) { return std::fwrite(bytes, 1, size_t(len), static_cast<FilteredPass *>(user)->f) == size_t(len) ? 0 : 1; }
 	[[noreturn]] void other_files(const std::string &what) const {
 		throw std::runtime_error("Filtered BAM output (-F): " + what + ": these are not the files the container was filled from (the same files, in the same order)");
 	}
+	// the compressor's leftover goes out (flags: DROPEST_DEFLATE_EOF behind the last one), its account is kept and it goes
+	void retire_compressor(int flags) {
+		if (dropest_deflate_stream_finish(z, flags)) throw std::runtime_error(std::string(dropest_deflate_last_error()) + ": " + name);
+		uint64_t in = 0, out = 0, batches = 0;
+		double ms = 0;
+		(void)dropest_deflate_stream_stats(z, &ms, &in, &out, &batches);
+		z_in += in; z_out += out; z_batches += batches; z_ms += ms;
+		dropest_deflate_stream_destroy(z); z = nullptr;
+	}
+	// sharded: the shard whose range holds read `ordinal` (past the last read, or no reads at all: the last shard that has any, else the first)
+	size_t shard_of(uint64_t ordinal) const {
+		size_t last = 0;
+		for (size_t k = 0; k < pieces.size(); ++k) {
+			if (!pieces[k].n) continue;
+			if (ordinal >= pieces[k].first && ordinal - pieces[k].first < pieces[k].n) return k;
+			last = k;
+		}
+		return last;
+	}
 };
 
-FilteredPass *filtered_pass_open(const BamSwitches &sw, CellsDataContainer &container, BamController::FilteredFile &report) {
-	// (a sharded or split container has no one context that holds every read: a shard's context says so in the read corrections' own words)
+// -F over the shards: every shard's decisions and the range it holds, the summed counts
+static void shards_decisions(FilteredPass &p, CellsDataContainer &container) {
+	const std::vector<dropest_shard *> &shards = container.shards();
+	auto refuse = [] { throw std::runtime_error(std::string("Filtered BAM output (-F): ") + dropest_last_error()); };      // (the shards' own words)
+	if (dropest_shard_group_read_corrections(shards.data(), int32_t(shards.size())) != DROPEST_OK) refuse();
+	uint64_t base = 0;
+	for (size_t k = 0; k < shards.size(); ++k) {
+		FilteredPass::Piece q{shards[k], container.shard_device(k), dropest_stream(dropest_shard_ctx(shards[k])), 0, 0, nullptr, nullptr, nullptr};
+		if (dropest_shard_read_corrections(q.shard, &q.n, &q.first, &q.verdict, &q.column, &q.umi) != DROPEST_OK) refuse();
+		// (the ranges ascend with the rank and leave no gap: a window is cut where they meet)
+		if (q.n && q.first != base) throw std::runtime_error("Filtered BAM output (-F): internal: shard " + std::to_string(k) + " holds the reads from " + std::to_string(q.first) + " on, the shards before it end at " + std::to_string(base));
+		if (!q.n) q.first = base;
+		base += q.n;
+		p.pieces.push_back(q);
+	}
+	p.n_reads = base;
+	if (dropest_shard_group_read_correction_counts(shards.data(), int32_t(shards.size()), p.counts) != DROPEST_OK) refuse();
+	const uint64_t *codes = nullptr;
+	if (dropest_shard_filtered_barcodes_device(shards[0], &p.n_cells, &codes) != DROPEST_OK) refuse();      // (n_cells: the columns; every file asks its own shard for the array)
+}
+
+FilteredPass *filtered_pass_open(const BamSwitches &sw, CellsDataContainer &container, BamController::FilteredFile &report, bool sharded_output) {
+	// (a sharded or split container has no one context that holds every read: without the switch a shard's context says so in the read
+	// corrections' own words)
 	dropest_ctx *const ctx = container.sharded() ? dropest_shard_ctx(container.shard0()) : container.handle();
 	std::unique_ptr<FilteredPass> p(new FilteredPass(sw, container, report));
-	if (!ctx || dropest_read_corrections(ctx, &p->n_reads, &p->d_verdict, &p->d_cell, &p->d_umi) != DROPEST_OK ||
+	const auto t_open = clk::now();
+	struct Note { double &ms; clk::time_point t; ~Note() { ms = since(t); } } note{p->decisions_ms, t_open};
+	if (container.sharded() && sharded_output) shards_decisions(*p, container);
+	else if (!ctx || dropest_read_corrections(ctx, &p->n_reads, &p->d_verdict, &p->d_cell, &p->d_umi) != DROPEST_OK ||
 	    dropest_cell_barcodes_device(ctx, &p->n_cells, &p->d_cell_codes) != DROPEST_OK || dropest_read_correction_counts(ctx, p->counts) != DROPEST_OK)
 		throw std::runtime_error(std::string("Filtered BAM output (-F): ") + (ctx ? dropest_last_error() : "the container holds no reads"));
 	if (p->n_cells > 0xFFFFFFFFull) throw std::runtime_error("Filtered BAM output (-F): more than 2^32 cells");
@@ -124,18 +181,16 @@ void filtered_pass_close(FilteredPass *pass, bool ok) {
 		if (p->at != p->n_reads) p->other_files("the files hold " + std::to_string(p->at) + " accepted reads, the container " + std::to_string(p->n_reads));
 		if (p->written != p->counts[0]) throw std::runtime_error("internal: " + std::to_string(p->written) + " reads were written to the filtered BAM file, the container's decisions write " + std::to_string(p->counts[0]));
 		if (!p->z) throw std::runtime_error("internal: no filtered BAM file was opened");
-		if (dropest_deflate_stream_finish(p->z, DROPEST_DEFLATE_EOF)) throw std::runtime_error(std::string(dropest_deflate_last_error()) + ": " + p->name);
-		uint64_t in = 0, out = 0, batches = 0;
-		double deflate_ms = 0;
-		(void)dropest_deflate_stream_stats(p->z, &deflate_ms, &in, &out, &batches);
-		dropest_deflate_stream_destroy(p->z); p->z = nullptr;
+		p->retire_compressor(DROPEST_DEFLATE_EOF);
+		const uint64_t in = p->z_in, out = p->z_out, batches = p->z_batches;
+		const double deflate_ms = p->z_ms;
 		const bool closed = std::fclose(p->f) == 0;
 		p->f = nullptr;
 		if (!closed) { std::remove(p->name.c_str()); throw std::runtime_error("Can't write filtered BAM file: " + p->name); }
 		r.name = p->name; r.windows = p->windows; r.total_reads = size_t(p->at); r.written = size_t(p->written);
 		r.wrong_genes = size_t(p->counts[3]); r.wrong_umis = size_t(p->counts[4]);
 		r.inflated_bytes = size_t(in); r.compressed_bytes = size_t(out); r.batches = size_t(batches);
-		r.decode_ms = p->decode_ms; r.tag_ms = p->tag_ms; r.deflate_ms = deflate_ms;
+		r.decode_ms = p->decode_ms; r.tag_ms = p->tag_ms; r.deflate_ms = deflate_ms; r.decisions_ms = p->decisions_ms;
 	} catch (...) { drop(); throw; }
 }
 
@@ -452,18 +507,32 @@ void DeviceFileReader::open_filtered() {
 	dropest_bam_filter_cfg fc{};
 	fc.out_tag[0] = RecordParser::tag16(parser.tags.cell_barcode); fc.out_tag[1] = RecordParser::tag16(parser.tags.umi);
 	fc.on_device = 1; fc.cell_barcode = P.d_cell_codes; fc.n_cells = uint32_t(P.n_cells);
+	if (!P.pieces.empty()) {      // sharded: the columns' barcodes, the copy on this decoder's GPU
+		uint64_t n_columns = 0;
+		if (dropest_shard_filtered_barcodes_device(P.pieces[P.cur].shard, &n_columns, &fc.cell_barcode) != DROPEST_OK) throw std::runtime_error(std::string("Filtered BAM output (-F): ") + dropest_last_error());
+		if (n_columns != P.n_cells) throw std::runtime_error("Filtered BAM output (-F): internal: the shards name different numbers of columns");
+	}
 	fc.n_side = uint32_t(P.side_off.size() - 1); fc.side_off = P.side_off.data(); fc.side_pool = P.side_pool.data();
 	if (dropest_bam_decoder_set_filtering(dec, &fc)) fail();
-	if (P.f) return;
-	std::string name = file.bam_name.substr(0, file.bam_name.find_last_of('.')) + ".filtered.bam";
-	const size_t slash = name.find_last_of("\\/");
-	if (slash != std::string::npos) name = name.substr(slash + 1);
-	P.name = name;
-	P.f = std::fopen(name.c_str(), "wb");
-	if (!P.f) throw std::runtime_error("Can't write filtered BAM file: " + name);
-	if (dropest_deflate_stream_create(target.device, dropest_bam_decoder_stream(dec), sw.tagged_batch, FilteredPass::write, &P, &P.z) ||
-	    dropest_deflate_stream_put(P.z, header_bytes.data(), header_bytes.size(), 0))
-		throw std::runtime_error(std::string(dropest_deflate_last_error()) + ": " + name);
+	// The compressor runs where the decoder does.  One context lends every file's decoder the same stream, and one compressor serves the call;
+	// a file of a sharded run whose first read lives with another shard brings another stream (another GPU, even): the compressor's leftover
+	// then goes out as a short block and a new one follows the decoder, so that the bytes need no ordering between two streams.
+	void *const st = dropest_bam_decoder_stream(dec);
+	if (P.z && (P.z_device != target.device || P.z_stream != st)) P.retire_compressor(0);
+	const bool first_file = !P.f;
+	if (first_file) {
+		std::string name = file.bam_name.substr(0, file.bam_name.find_last_of('.')) + ".filtered.bam";
+		const size_t slash = name.find_last_of("\\/");
+		if (slash != std::string::npos) name = name.substr(slash + 1);
+		P.name = name;
+		P.f = std::fopen(name.c_str(), "wb");
+		if (!P.f) throw std::runtime_error("Can't write filtered BAM file: " + name);
+	}
+	if (!P.z) {
+		if (dropest_deflate_stream_create(target.device, st, sw.tagged_batch, FilteredPass::write, &P, &P.z)) throw std::runtime_error(std::string(dropest_deflate_last_error()) + ": " + P.name);
+		P.z_device = target.device; P.z_stream = st;
+	}
+	if (first_file && dropest_deflate_stream_put(P.z, header_bytes.data(), header_bytes.size(), 0)) throw std::runtime_error(std::string(dropest_deflate_last_error()) + ": " + P.name);
 }
 
 // (g) -F: the window the decoder holds under the decisions of its accepted records -- entries [at, at + n_accepted) of the container's, where they are
@@ -473,8 +542,21 @@ void DeviceFileReader::filter_window(const dropest_bam_window &w) {
 	if (n > P.n_reads - P.at) P.other_files("a window of " + file.bam_name + " brings the accepted reads to " + std::to_string(P.at + n) + ", the container holds " + std::to_string(P.n_reads));
 	const uint8_t *d_out = nullptr;
 	uint64_t len = 0, written = 0;
-	int rc = dropest_bam_decoder_filter_window(dec, P.d_verdict + P.at, P.d_cell + P.at, P.d_umi + P.at, n, 1, &d_out, &len, &written);
-	if (rc == 2) { patch_host_decided(w); rc = dropest_bam_decoder_filter_window(dec, P.d_verdict + P.at, P.d_cell + P.at, P.d_umi + P.at, n, 1, &d_out, &len, &written); }
+	// sharded: [at, at + n) cut at the boundaries of the shards' ranges -- every shard whose range meets or touches the window gives one segment
+	// (an empty one where it only touches, or holds no reads)
+	std::vector<dropest_bam_decision_segment> segs;
+	for (const FilteredPass::Piece &q : P.pieces) {
+		const uint64_t lo = std::max(P.at, q.first), hi = std::min(P.at + n, q.first + q.n);
+		if (lo > hi) continue;
+		const uint64_t skip = lo - q.first;
+		segs.push_back(dropest_bam_decision_segment{hi - lo, q.verdict + skip, q.column + skip, q.umi + skip, int32_t(q.device)});
+	}
+	auto filter = [&] {
+		return P.pieces.empty() ? dropest_bam_decoder_filter_window(dec, P.d_verdict + P.at, P.d_cell + P.at, P.d_umi + P.at, n, 1, &d_out, &len, &written)
+		                        : dropest_bam_decoder_filter_window_segments(dec, segs.data(), uint32_t(segs.size()), &d_out, &len, &written);
+	};
+	int rc = filter();
+	if (rc == 2) { patch_host_decided(w); rc = filter(); }
 	if (rc) fail();
 	if (len && dropest_deflate_stream_put(P.z, d_out, len, 1)) throw std::runtime_error(std::string(dropest_deflate_last_error()) + ": " + P.name);
 	P.at += n; P.written += written; ++P.windows;
@@ -861,7 +943,12 @@ bool read_file_on_device(FileIngest &file) {
 	if (parser.gene_in_chromosome_name) { file.refusal = "gene = chromosome name is resolved by the host reader"; return false; }
 	// (-b stays here whatever the container takes: a window it cannot take in bulk goes through records_through_host, record by record if need be)
 	if (!file.tagged && !file.filtered && !file.container.bulk_ingest_possible_at_all(true)) { file.refusal = "the container no longer takes reads in bulk"; return false; }
-	const CellsDataContainer::IngestTarget target = file.container.next_read_target();
+	CellsDataContainer::IngestTarget target = file.container.next_read_target();
+	if (file.filtered && !file.filtered->pieces.empty()) {      // -F over shards: the decoder sits with the shard that holds the file's first read, on its stream, as ingest does
+		FilteredPass &P = *file.filtered;
+		P.cur = P.shard_of(P.at);
+		target.device = P.pieces[P.cur].device; target.stream = P.pieces[P.cur].stream;
+	}
 	const auto t_enter = clk::now();
 	if (parser.tags.intronic_read_value.size() > 24 || parser.tags.intergenic_read_value.size() > 24) { file.refusal = "a read-type value is longer than 24 bytes"; return false; }
 	DeviceFileReader reader(file, target, t_enter);

@@ -97,6 +97,7 @@ public:
 		size_t wrong_genes = 0, wrong_umis = 0;              // FilteringBamProcessor::trace_state's numbers (dropest_read_correction_counts [3], [4])
 		size_t inflated_bytes = 0, compressed_bytes = 0, batches = 0;
 		double decode_ms = 0, tag_ms = 0, deflate_ms = 0;    // the decoder's kernels and copies, the tag kernels, the compressor's launches: by device events
+		double decisions_ms = 0;                             // host time of the read corrections (one context's, or all shards'), paid once before the first file
 	};
 private:
 	BamTags _tags;
@@ -111,6 +112,7 @@ private:
 	int _min_barcode_phred;
 	unsigned _threads;
 	bool _device_decode = false;
+	bool _sharded_filtered_output = false;
 	Counters _counters;
 	std::vector<TaggedFile> _tagged;
 	FilteredFile _filtered;
@@ -140,9 +142,15 @@ public:
 	// readers accept, so the files must be the ones the container was filled from, in that order: a window that would pass the container's
 	// read count, or a final count that differs from it, throws std::runtime_error saying so; and when this controller filled the container
 	// (its last parse_bam_files call accepted exactly the container's reads) every file must bring the reads it brought then.  Device path only, like -b: -r parameter files,
-	// gene = chromosome name, a read-type value over 24 bytes, no GPU throw naming the reason; a sharded or split container and UMI-dictionary
-	// mode throw with the read corrections' own message.
+	// gene = chromosome name, a read-type value over 24 bytes, no GPU throw naming the reason; a sharded or split container (unless
+	// set_sharded_filtered_output is on) and UMI-dictionary mode throw with the read corrections' own message.
 	void write_filtered_bam_files(const std::vector<std::string> &bam_files, CellsDataContainer &container);
+	// -F over a sharded or split container (off by default: write_filtered_bam_files then refuses such a container as before).  On: the shards
+	// compute their reads' decisions (dropest_shard_group_read_corrections), every window is filtered under the pieces of them that the shards'
+	// resident ranges cut out of it (dropest_bam_decoder_filter_window_segments), each file's decoder sits on the GPU and stream of the shard that
+	// holds the file's first read, and the one output is what one context would have written.  What the shards' read corrections refuse
+	// (UMI-dictionary mode, a molecule key wider than 64 bits, ...) throws in their words.  DESIGN.md section 7.
+	void set_sharded_filtered_output(bool on) { _sharded_filtered_output = on; }
 	const FilteredFile &filtered_file() const { return _filtered; }           // of the last write_filtered_bam_files call (empty when it threw)
 	// BGZF inflate, record chain and tag walk on the container's GPU (include/dropest_bgzf.h) where the configuration allows it: tags or read
 	// names as the source of barcode / UMI, the gene tag or a -g annotation (annotation_api.hip) as the source of the gene; not with -r or gene =

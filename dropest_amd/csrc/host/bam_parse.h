@@ -311,8 +311,10 @@ struct FileIngest {
 // -F (bam_device.cpp): what the files of one write_filtered_bam_files call share -- the container's decisions on the device, the running count of
 // accepted records, the one output and its compressor.  _open throws what the read corrections refuse; _close(ok): what is left over, the
 // end-of-file block and the account in `report` when ok, else the output is removed and `report` left empty.
+// sharded_output (BamController::set_sharded_filtered_output): a sharded or split container's decisions are its shards', one piece of the stream
+// each; off, such a container is handed to the one-context call, which refuses it.
 struct FilteredPass;
-FilteredPass *filtered_pass_open(const BamSwitches &sw, CellsDataContainer &container, BamController::FilteredFile &report);
+FilteredPass *filtered_pass_open(const BamSwitches &sw, CellsDataContainer &container, BamController::FilteredFile &report, bool sharded_output);
 void filtered_pass_close(FilteredPass *pass, bool ok);
 uint64_t filtered_pass_reads(const FilteredPass *pass);      // accepted records of the files read so far
 uint64_t filtered_pass_total(const FilteredPass *pass);      // the container's reads

@@ -400,6 +400,9 @@ public:
 	// container at set_initialized(): the same reads as 2^k shards on that device (dropest_ctx_split), same restrictions.
 	bool sharded() const { return !_shards.empty(); }
 	dropest_shard *shard0() const { return _shards.empty() ? nullptr : _shards[0]; }
+	// every shard, in the order of their ranges of the stream, and the GPU each sits on (a split container: all on the container's device)
+	const std::vector<dropest_shard *> &shards() const { return _shards; }
+	int shard_device(size_t k) const { return _shard_devices.size() == _shards.size() ? _shard_devices[k] : _device; }
 	// (source, target) barcodes of the cells the CB merge folded: merge_targets() by barcode, also on a sharded container
 	std::vector<std::pair<std::string, std::string>> merged_barcodes() const;
 	~CellsDataContainer();

@@ -32,6 +32,9 @@
 // wave-uniform loads (rank, verdict, cell, the cell's code, the UMI code) in front of a walk of ~15 entries, and a record that is not written
 // costs nothing else.  Everything a decision points at is checked before it is
 // loaded: a cell id or a side-string index out of range sets BAMTAG_FLAG_RANGE and the record gets size 0.
+// Where the decisions stand is a template parameter of the decision (SRC, as read_corrections_kernel takes its look-up): BamTagOneArray, entry
+// rank[r] of one array -- one context's -- or BamTagSegments, a table of segments in device memory, one per shard of a sharded run whose resident
+// range meets the window; the segment of a rank is found by a ballot over 64 table entries a step, wave-uniform like everything else here.
 // Measured: rank + plan + scan + emit 64.5 ms for 16 M records of which 13.7 M are written (-b in the same job: 59.1 ms for all 16 M);
 // 3-9 % of the -F pass, of which the compressor is 71-81 %.
 #pragma once
@@ -66,6 +69,14 @@ struct BamTagFilt {
 	const uint32_t *side_off; const uint8_t *side_pool; uint32_t n_side;  // the strings of escaped codes: string k = pool[off[k] .. off[k + 1])
 	uint32_t out_tag[2];                                                  // corrected barcode, corrected UMI (0 = never written)
 };
+// -F, decisions in segments (a sharded run: read i's decision lives in the arrays of the shard whose resident range holds ordinal i, and a window
+// crosses up to one boundary per shard): segment s holds the decisions of the accepted ranks [first, first + count) of the window, entry
+// k - first of its arrays.  `first` ascends (it is the sum of the counts before), a count of 0 is legal anywhere.  The table lives in device
+// memory (64 entries would be 2 KB of kernel arguments); the arrays belong to the decoder's GPU.
+struct BamTagSeg { uint32_t first, count; const uint8_t *verdict; const uint32_t *cell; const uint64_t *umi; };
+static_assert(sizeof(BamTagSeg) == 32, "one table entry is 32 bytes");
+// where the decision of accepted rank k stands (all three wave-uniform)
+struct BamTagEntry { const uint8_t *verdict; const uint32_t *cell; const uint64_t *umi; };
 // a value of -F as the record function takes it: len characters, of a side string (str) or spelled from a plain code
 struct BamTagValue { const uint8_t *str; unsigned long long code; uint32_t len; };
 struct BamTagFix { uint32_t name[2]; BamTagValue v[2]; };
@@ -308,37 +319,78 @@ __device__ inline bool bamtag_value(unsigned long long code, const BamTagFilt &f
 	return true;
 }
 
-// Record r of the window: false = not written (not accepted, or a verdict that is not 0, or a decision that points outside its tables: flagged)
-__device__ inline bool bamtag_decision(const BamTagIn &in, const BamTagFilt &f, uint32_t r, BamTagFix &fx, uint32_t *flags, uint32_t lane) {
+// The two sources of a decision (bamtag_decision's SRC, as read_corrections_kernel takes its look-up): entry(f, k, lane, e) = where rank k's
+// decision stands; false: no decision covers k (nothing is loaded from there).
+// BamTagOneArray: entry k of BamTagFilt's own arrays -- no load, no branch.
+struct BamTagOneArray {
+	__device__ bool entry(const BamTagFilt &f, uint32_t k, uint32_t, BamTagEntry &e) const {
+		e.verdict = f.verdict + k; e.cell = f.cell + k; e.umi = f.umi + k;
+		return k < f.n;                                                // (always: the caller checked the window's accepted count)
+	}
+};
+// BamTagSegments: the segment that covers k, by wave-uniform work alone -- 64 entries of the table a step, one per lane, and a ballot over
+// first <= k < first + count (at most one lane answers: the segments do not overlap; an empty one never does); the table ascends, so the
+// search ends at the first step that holds an entry beginning behind k.  Then the entry's three pointers, loaded by the whole wave from one address.
+// A window of a sharded run has one segment per shard: one step, one 8-byte load per lane and three uniform ones more than the one array.
+struct BamTagSegments {
+	const BamTagSeg *seg; uint32_t n_seg;
+	__device__ bool entry(const BamTagFilt &, uint32_t k, uint32_t lane, BamTagEntry &e) const {
+		for (uint32_t base = 0; base < n_seg; base += 64u) {
+			const uint32_t s = base + lane;
+			uint32_t first = 0xFFFFFFFFu, count = 0;
+			if (s < n_seg) { first = seg[s].first; count = seg[s].count; }
+			const uint64_t hit = __ballot(first <= k && k - first < count);
+			if (hit) {
+				const BamTagSeg &g = seg[base + uint32_t(__ffsll((long long)hit) - 1)];
+				const uint32_t j = k - bt_u(g.first);
+				e.verdict = reinterpret_cast<const uint8_t *>(bt_u64(reinterpret_cast<unsigned long long>(g.verdict))) + j;
+				e.cell = reinterpret_cast<const uint32_t *>(bt_u64(reinterpret_cast<unsigned long long>(g.cell))) + j;
+				e.umi = reinterpret_cast<const uint64_t *>(bt_u64(reinterpret_cast<unsigned long long>(g.umi))) + j;
+				return true;
+			}
+			if (__ballot(s < n_seg && first > k)) break;
+		}
+		return false;
+	}
+};
+
+// Record r of the window: false = not written (not accepted, or a verdict that is not 0, or a decision that points outside its tables, or no
+// decision at all: flagged)
+template <class SRC>
+__device__ inline bool bamtag_decision(const BamTagIn &in, const BamTagFilt &f, const SRC &src, uint32_t r, BamTagFix &fx, uint32_t *flags, uint32_t lane) {
 	if (bt_u(in.status[r]) != BAM_OK) return false;
 	const uint32_t k = bt_u(f.rank[r]);
-	bool ok = k < f.n;                                             // (always: the caller checked the window's accepted count)
-	if (ok && bt_u(f.verdict[k]) != 0u) return false;
+	BamTagEntry e;
+	bool ok = src.entry(f, k, lane, e);
+	if (ok && bt_u(*e.verdict) != 0u) return false;
 	uint32_t cell = 0;
-	if (ok) { cell = bt_u(f.cell[k]); ok = cell < f.n_cells; }
+	if (ok) { cell = bt_u(*e.cell); ok = cell < f.n_cells; }
 	if (ok) ok = bamtag_value(bt_u64(f.cell_barcode[cell]), f, fx.v[0]);
-	if (ok) ok = bamtag_value(bt_u64(f.umi[k]), f, fx.v[1]);
+	if (ok) ok = bamtag_value(bt_u64(*e.umi), f, fx.v[1]);
 	if (!ok) { if (lane == 0) atomicOr(flags, BAMTAG_FLAG_RANGE); return false; }
 	fx.name[0] = f.out_tag[0]; fx.name[1] = f.out_tag[1];
 	return true;
 }
 
-// bam_tag_plan_kernel / bam_tag_emit_kernel for -F
+// bam_tag_plan_kernel / bam_tag_emit_kernel for -F; SRC: BamTagOneArray (one context) or BamTagSegments (the shards of a sharded run), the last
+// argument so that no other one moves
+template <class SRC>
 __global__ __launch_bounds__(BAMTAG_T) void bam_tag_filter_plan_kernel(BamTagIn in, BamParseCfg pc, BamTagCfg tc, BamTagNames names, BamTagFilt filt, uint32_t *__restrict__ size,
-                                                                        uint32_t *__restrict__ flags) {
+                                                                        uint32_t *__restrict__ flags, SRC src) {
 	const uint32_t lane = threadIdx.x & 63u;
 	const uint32_t r = bt_u(blockIdx.x * BAMTAG_WAVES + (threadIdx.x >> 6));
 	if (r >= in.n_rec) return;
 	uint32_t mark, g_len; const uint8_t *g; bool use_override, over = false;
 	uint32_t bytes = 0;
 	BamTagFix fx;
-	if (bamtag_decision(in, filt, r, fx, flags, lane) && bamtag_inputs(in, names, r, mark, g, g_len, use_override, flags, lane))
+	if (bamtag_decision(in, filt, src, r, fx, flags, lane) && bamtag_inputs(in, names, r, mark, g, g_len, use_override, flags, lane))
 		bytes = bamtag_record<false, true>(in.data + in.rec_off[r], lane, pc, tc, mark, g, g_len, use_override, nullptr, 0u, over, fx);
 	if (lane == 0) size[r] = bytes;
 }
 
+template <class SRC>
 __global__ __launch_bounds__(BAMTAG_T) void bam_tag_filter_emit_kernel(BamTagIn in, BamParseCfg pc, BamTagCfg tc, BamTagNames names, BamTagFilt filt, const uint32_t *__restrict__ size,
-                                                                        const uint64_t *__restrict__ out_off, uint8_t *__restrict__ out, uint64_t out_total, uint32_t *__restrict__ flags) {
+                                                                        const uint64_t *__restrict__ out_off, uint8_t *__restrict__ out, uint64_t out_total, uint32_t *__restrict__ flags, SRC src) {
 	const uint32_t lane = threadIdx.x & 63u;
 	const uint32_t r = bt_u(blockIdx.x * BAMTAG_WAVES + (threadIdx.x >> 6));
 	if (r >= in.n_rec) return;
@@ -348,7 +400,7 @@ __global__ __launch_bounds__(BAMTAG_T) void bam_tag_filter_emit_kernel(BamTagIn 
 	if (at + cap > out_total) { if (lane == 0) atomicOr(flags, BAMTAG_FLAG_SIZE); return; }
 	uint32_t mark, g_len; const uint8_t *g; bool use_override, over = false;
 	BamTagFix fx;
-	if (!bamtag_decision(in, filt, r, fx, flags, lane) || !bamtag_inputs(in, names, r, mark, g, g_len, use_override, flags, lane)) return;
+	if (!bamtag_decision(in, filt, src, r, fx, flags, lane) || !bamtag_inputs(in, names, r, mark, g, g_len, use_override, flags, lane)) return;
 	bamtag_record<true, true>(in.data + in.rec_off[r], lane, pc, tc, mark, g, g_len, use_override, out + at, cap, over, fx);
 	if (over && lane == 0) atomicOr(flags, BAMTAG_FLAG_SIZE);
 }

@@ -1,5 +1,6 @@
 // shard_read_corrections.h -- per-read corrected cell barcode and UMI (`dropest -F`, the DECISIONS: read_corrections.h, k_readfix.h) for the
-// shards of a sharded or split run (included by shard_run.h).  The file writer on top of them is not built for shards.
+// shards of a sharded or split run (included by shard_run.h).  The file writer on top of them: host/bam_device.cpp (FilteredPass's second shape,
+// behind BamController::set_sharded_filtered_output), which feeds every window the pieces of these arrays that the shards' ranges cut out of it.
 //
 // After a step a shard still holds its contiguous range of the stream (r_cb / r_umi / r_gene, n_res reads from first_ordinal on), the global
 // table G and cm's column order.  A read's barcode is usually owned by another shard, and the cell it was merged into by a third, so:

@@ -217,6 +217,23 @@ int dropest_bam_decoder_set_filtering(dropest_bam_decoder *d, const dropest_bam_
  * window afterwards still gives the -b bytes. */
 int dropest_bam_decoder_filter_window(dropest_bam_decoder *d, const uint8_t *verdict, const uint32_t *cell, const uint64_t *umi, uint64_t n, int on_device,
                                       const uint8_t **d_out, uint64_t *len, uint64_t *n_written);
+/* .._filter_window for decisions that stand in SEGMENTS, as the shards of a sharded run hold them (dropest_shard_read_corrections, dropest_amd.h:
+ * read i's decision lives with the shard whose resident range holds ordinal i, and a window crosses up to one boundary per shard).  Segment s
+ * holds the decisions of the next `count` accepted records of the window, entry 0 first; the counts must sum to the window's n_accepted, a count
+ * of 0 is legal anywhere (its pointers are not looked at).  The arrays are DEVICE memory of GPU `device`, finished (nothing queued still writes
+ * them).  Segments on the decoder's GPU are read where they are -- only the table of segments travels, through the decoder's pinned staging;
+ * segments on another GPU are copied into the decoder's staging first, on its stream (that hop has never run: DESIGN.md section 7;
+ * DROPEST_BAM_TEST_STAGE_SEGMENTS=1 sends every segment through the staging).  A decision's `cell` indexes the cell_barcode table of
+ * .._set_filtering, whatever that table lists (a sharded run: the columns of dropest_shard_filtered_barcodes_device).  Returns as .._filter_window. */
+typedef struct dropest_bam_decision_segment {
+	uint64_t count;
+	const uint8_t *verdict;
+	const uint32_t *cell;
+	const uint64_t *umi;
+	int32_t device;
+} dropest_bam_decision_segment;
+int dropest_bam_decoder_filter_window_segments(dropest_bam_decoder *d, const dropest_bam_decision_segment *seg, uint32_t n_seg, const uint8_t **d_out, uint64_t *len,
+                                               uint64_t *n_written);
 /* The hipStream_t the decoder's kernels run on (lent or its own): work a caller queues there follows the tagged bytes in order. */
 void *dropest_bam_decoder_stream(dropest_bam_decoder *d);
 
