@@ -182,6 +182,19 @@ struct BamTagging {
 	void reset() { on = false; has_names = false; pending = false; len = 0; ms = 0; bytes_in = bytes_out = 0; filt.on = false; }      // (the names were the annotation's)
 };
 
+// The two sources beside a record's own tags and name (k_bamparse.h: BamSources): the caller's read-parameter table (-r; not owned) with the
+// stream ordinal of the next window's first record, and the reference -> gene table of -P.  A reset drops both, as it drops the annotation.
+struct BamSourceState {
+	dropest_read_params *table = nullptr;
+	uint64_t first_ordinal = 0, seen = 0;      // seen: records of the windows finished since the table was given
+	bool ref_gene = false;
+	DevBuf<uint32_t> rp_row;
+	DevBuf<int32_t> gene_of_ref;
+	PinnedBuf<uint32_t> h_rp_row;
+	void reset() { table = nullptr; first_ordinal = seen = 0; ref_gene = false; }
+	int bits() const { return (table ? BAM_SRC_PARAMS : 0) | (ref_gene ? BAM_SRC_REF_GENE : 0); }
+};
+
 // Where the file's windows stand: the record the last chain cut off, the fronts' turns, what the last finished window holds
 struct BamProgress {
 	uint64_t tail_len = 0, last_n_rec = 0, last_n_ok = 0;
@@ -213,6 +226,7 @@ struct dropest_bam_decoder {
 	BamGather gather;
 	BamUpload up;
 	BamTagging tag;
+	BamSourceState src;
 
 	BamFront &last() { return front[at.last_front]; }
 	// room for n records in tiles of BAM_FIN_TILE (`tiles` of them); the annotation's columns when there is one
@@ -221,6 +235,7 @@ struct dropest_bam_decoder {
 		dense.cb.ensure(n); dense.umi.ensure(n); dense.gene.ensure(n); dense.aux.ensure(n); dense.qoff.ensure(n); dense.need_rec.ensure(n); dense.need_pos.ensure(n); dense.need_size.ensure(n);
 		rec.tile_ok.ensure(tiles); rec.tile_need.ensure(tiles); rec.d_totals.ensure(2); rec.d_wc.ensure(1);
 		if (dict.annotation) { ann.chr.ensure(n); ann.pos.ensure(n); ann.end.ensure(n); ann.gene.ensure(n); ann.mark.ensure(n); }
+		if (src.table) src.rp_row.ensure(n);
 	}
 	BamRecordOut record_out() const { return BamRecordOut{rec.cb.p, rec.umi.p, rec.gene.p, rec.aux.p, rec.uql.p, rec.qoff.p, rec.status.p, rec.need.p, ann.chr.p, ann.pos.p, ann.end.p}; }
 };
@@ -288,7 +303,7 @@ extern "C" int dropest_bam_decoder_reset(dropest_bam_decoder *d, const dropest_b
 		for (BamFront &f : d->front) { if (f.stream) HIP_CHECK(hipStreamSynchronize(f.stream)); f.begun = false; f.inflating = false; }
 		HIP_CHECK(hipStreamSynchronize(d->up.stream));
 		std::memcpy(&d->cfg, cfg, sizeof(BamParseCfg));
-		d->up.reset(); d->at = BamProgress{}; d->tag.reset(); d->dict.reset(cfg->n_refs);
+		d->up.reset(); d->at = BamProgress{}; d->tag.reset(); d->src.reset(); d->dict.reset(cfg->n_refs);
 		queue_empty_dictionaries(d);
 		HIP_CHECK(hipStreamSynchronize(d->stream));
 	});

@@ -98,3 +98,38 @@ extern "C" int dropest_bam_decoder_set_dictionaries(dropest_bam_decoder *d, cons
 		D.g_mask = cap - 1;
 	});
 }
+
+// -r: the records' barcodes, UMIs and UMI quality strings come from `table` (dropest_read_params_*, bam_read_params.h; built, on this GPU; it stays
+// the caller's and outlives the decoder's use of it) by the read's name, each row serving the first record of the stream that asks for it.
+// first_ordinal: the stream ordinal of the next window's first record -- above every ordinal that claimed a row of this table before (the records
+// of the files read so far).  NULL turns the source off; so does a reset.  Not with -f (the tags win there), not with tagged output.
+extern "C" int dropest_bam_decoder_set_read_params(dropest_bam_decoder *d, dropest_read_params *table, uint64_t first_ordinal) {
+	return bgzf_guarded([&] {
+		if (!d) throw InvalidError("null argument");
+		if (!table) { d->src.table = nullptr; return; }
+		if (!table->built) throw InvalidError("the read-parameter table was not built (dropest_read_params_build)");
+		if (table->device != d->device) throw InvalidError("the read-parameter table lives on another GPU");
+		if (d->cfg.filled_bam) throw InvalidError("read-parameter files are not looked at under -f (barcode and UMI come from the tags)");
+		if (d->tag.on) throw UnsupportedError("tagged output is not written under read-parameter files");
+		d->src.table = table; d->src.first_ordinal = first_ordinal; d->src.seen = 0;
+	});
+}
+
+// -P: the gene of a record is its reference's name.  gene_of_ref[r] = the index of reference r's name in the caller's gene dictionary, -1 = not in
+// it yet (a record on r comes back through need_*; call again once the dictionary has grown), -2 = the name is empty (no gene, mark 0).  The gene
+// tag, the read type and an annotation are then not looked at.  NULL turns the source off; so does a reset.
+extern "C" int dropest_bam_decoder_set_gene_of_reference(dropest_bam_decoder *d, const int32_t *gene_of_ref, uint32_t n_refs) {
+	return bgzf_guarded([&] {
+		if (!d) throw InvalidError("null argument");
+		if (!gene_of_ref) { d->src.ref_gene = false; return; }
+		if (n_refs != uint32_t(d->cfg.n_refs)) throw InvalidError("one gene per reference is expected");
+		if (d->tag.on) throw UnsupportedError("tagged output is not written under gene = chromosome name");
+		for (uint32_t r = 0; r < n_refs; ++r) if (gene_of_ref[r] < -2) throw InvalidError("a gene index below -2");
+		HIP_CHECK(hipSetDevice(d->device));
+		bam_ready(d);
+		HIP_CHECK(hipStreamSynchronize(d->stream));
+		d->src.gene_of_ref.ensure(std::max<uint32_t>(n_refs, 1u));
+		if (n_refs) { size_t at = 0; d->dict.h_dict.ensure(size_t(n_refs) * 4 + 64); bam_to_device(d, d->src.gene_of_ref.p, gene_of_ref, size_t(n_refs) * 4, at); HIP_CHECK(hipStreamSynchronize(d->stream)); }
+		d->src.ref_gene = true;
+	});
+}

@@ -60,7 +60,7 @@ extern "C" int dropest_bam_decoder_quality_rows(dropest_bam_decoder *d, uint32_t
 		bam_ready(d);
 		BamDenseColumns &C = d->dense;
 		C.qual.ensure(n * ql + n * ql / 4); C.h_qual.ensure(n * ql);
-		hipLaunchKernelGGL(bam_quality_rows_kernel, dim3(uint32_t((n + 255) / 256)), dim3(256), 0, d->stream, d->last().data(), C.qoff.p, uint32_t(n), ql, C.qual.p);
+		hipLaunchKernelGGL(bam_quality_rows_kernel, dim3(uint32_t((n + 255) / 256)), dim3(256), 0, d->stream, d->last().data(), d->src.table ? d->src.table->text.p : (const uint8_t *)nullptr, C.qoff.p, uint32_t(n), ql, C.qual.p);
 		HIP_CHECK(hipGetLastError());
 		HIP_CHECK(hipMemcpyAsync(C.h_qual.p, C.qual.p, n * ql, hipMemcpyDeviceToHost, d->stream));
 		HIP_CHECK(hipStreamSynchronize(d->stream));
@@ -86,5 +86,25 @@ extern "C" int dropest_bam_decoder_patch(dropest_bam_decoder *d, const uint32_t 
 		hipLaunchKernelGGL(bam_patch_kernel, dim3((n + 255) / 256), dim3(256), 0, d->stream, q_pos, q_cb, q_umi, q_gene, q_aux, n, d->dense.args());
 		HIP_CHECK(hipGetLastError());
 		HIP_CHECK(hipStreamSynchronize(d->stream));
+	});
+}
+
+// -r: for records rec_idx[0 .. n) of the LAST window (NULL: its first n records) the row of the read-parameter table each was SERVED -- a row that
+// fails the quality filter too, which the record took and is "low quality" for; 0xFFFFFFFF for every other record
+extern "C" int dropest_bam_decoder_param_rows(dropest_bam_decoder *d, const uint32_t *rec_idx, uint32_t n, uint32_t *out_rows) {
+	return bgzf_guarded([&] {
+		if (!d || (n && !out_rows)) throw InvalidError("null argument");
+		if (!d->src.table) throw InvalidError("no read-parameter table was given to this decoder");
+		if (!n) return;
+		const uint64_t n_rec = d->at.last_n_rec;
+		if (!rec_idx && n > n_rec) throw RangeError("record index outside the window");
+		for (uint32_t k = 0; rec_idx && k < n; ++k) if (rec_idx[k] >= n_rec) throw RangeError("record index outside the window");
+		HIP_CHECK(hipSetDevice(d->device));
+		bam_ready(d);
+		PinnedBuf<uint32_t> &H = d->src.h_rp_row;
+		H.ensure(n_rec);
+		bam_copy(d->stream, uint32_t(n_rec), to_host(d->src.rp_row.p, H.p));
+		HIP_CHECK(hipStreamSynchronize(d->stream));
+		for (uint32_t k = 0; k < n; ++k) out_rows[k] = H.p[rec_idx ? rec_idx[k] : k];
 	});
 }

@@ -9,6 +9,7 @@ extern "C" int dropest_bam_decoder_set_tagging(dropest_bam_decoder *d, const dro
 		BamTagging &T = d->tag;
 		T.on = false; T.has_names = false; T.len = 0; T.filt.on = false;      // (-F is configured behind -b: its names are checked against these)
 		if (!cfg) return;
+		if (d->src.bits()) throw UnsupportedError("tagged output is not written under read-parameter files or gene = chromosome name");
 		static_assert(sizeof(BamTagCfg) == 12 + 12 + 72, "the C struct's first members and the kernels' struct are one layout");
 		for (int k = 0; k < 3; ++k) if (cfg->type_len[k] > 24) throw InvalidError("read-type values longer than 24 characters");
 		if (!cfg->out_tag[1] || !cfg->out_tag[2]) throw InvalidError("the raw barcode and raw UMI tags need two-letter names");

@@ -235,9 +235,21 @@ static void queue_fields(dropest_bam_decoder *d, BamFront &F, hipStream_t st, co
 	lap("buffers ensured");
 	const BamRecordOut ro = d->record_out();
 	const BamDict dict = d->dict.args();
-	dropest_annotation *const annotation = d->dict.annotation;
+	const int sources = d->src.bits();
+	dropest_annotation *const annotation = (sources & BAM_SRC_REF_GENE) ? nullptr : d->dict.annotation;      // (-P comes before -g)
 	if (annotation) HIP_CHECK(hipMemsetAsync(d->ann.chr.p, 0xFF, size_t(n_rec) * 4, st));   // (records that are not accepted: "no such chromosome", ignored)
-	hipLaunchKernelGGL(bam_parse_kernel, dim3(uint32_t((n_rec + BAM_PARSE_T - 1) / BAM_PARSE_T)), dim3(BAM_PARSE_T), 0, st, F.data(), d->rec.off.p, uint32_t(n_rec), d->cfg, dict, ro, F.d_bad.p);
+	const dim3 parse_grid(uint32_t((n_rec + BAM_PARSE_T - 1) / BAM_PARSE_T));
+	if (!sources) hipLaunchKernelGGL(bam_parse_kernel, parse_grid, dim3(BAM_PARSE_T), 0, st, F.data(), d->rec.off.p, uint32_t(n_rec), d->cfg, dict, ro, F.d_bad.p);
+	else {
+		// -r: the claims of this window's records carry ordinals behind those of every window before (the parses run in file order on one stream)
+		const BamSources bs{d->src.table ? d->src.table->view() : RpTable{}, d->src.first_ordinal + d->src.seen, d->src.rp_row.p, d->src.gene_of_ref.p};
+		auto parse = [&](auto kernel) { hipLaunchKernelGGL(kernel, parse_grid, dim3(BAM_PARSE_T), 0, st, F.data(), d->rec.off.p, uint32_t(n_rec), d->cfg, dict, ro, F.d_bad.p, bs); };
+		if (sources == BAM_SRC_PARAMS) parse(bam_parse_sources_kernel<BAM_SRC_PARAMS>);
+		else if (sources == BAM_SRC_REF_GENE) parse(bam_parse_sources_kernel<BAM_SRC_REF_GENE>);
+		else parse(bam_parse_sources_kernel<BAM_SRC_PARAMS | BAM_SRC_REF_GENE>);
+		if (sources & BAM_SRC_PARAMS) hipLaunchKernelGGL(bam_params_settle_kernel, dim3(uint32_t((n_rec + 255) / 256)), dim3(256), 0, st, uint32_t(n_rec), bs, ro, annotation ? 1 : 0);
+		d->src.seen += n_rec;
+	}
 	if (annotation) {
 		if (dropest_annotation_query_device(annotation, st, n_rec, d->ann.chr.p, d->ann.pos.p, d->ann.end.p, d->ann.gene.p, d->ann.mark.p)) throw DeviceError(dropest_annotation_last_error());
 		hipLaunchKernelGGL(bam_resolve_annotated_kernel, dim3(uint32_t((n_rec + 255) / 256)), dim3(256), 0, st, uint32_t(n_rec), dict, ro, d->ann.gene.p, d->ann.mark.p);

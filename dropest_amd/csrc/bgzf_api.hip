@@ -182,6 +182,7 @@ extern "C" void dropest_bgzf_warm_up(void *stream) {
 }
 
 // The device BAM decoder (dropest_bam_decoder_*), in this translation unit so that the one launch above loads its kernels as well
+#include "bam_read_params.h"        // -r: the read-parameter table, an object of its own beside the decoders
 #include "bam_decoder.h"            // the state, the shared helpers, its life cycle, buffer sizing
 #include "bam_decoder_dict.h"       // the dictionaries and the annotation
 #include "bam_decoder_upload.h"     // staging, pinned pieces, the compressed bytes sent ahead of the window call

@@ -21,46 +21,58 @@ BamController::BamController(const BamTags &tags, bool filled_bam, const std::st
 }
 
 // ReadMapParamsParser::init (ReadMapParamsParser.cpp:50-108): gzip text files, one "name cb umi cb_quality umi_quality" row per
-// read (ReadParameters::parse_from_string, ReadParameters.cpp:58-78); malformed rows and repeated names are reported and skipped
+// read (ReadParameters::parse_from_string, ReadParameters.cpp:58-78).  Here the files are only inflated and their lines found; who splits the
+// rows depends on the reader that takes the first file: map_read_params for the host reader, a kernel for the device path (ParamSource).
 void BamController::load_read_params(const std::string &filenames) {
 	_params_from_files = true;
+	_param_source = std::make_shared<ParamSource>();
+	ParamSource &src = *_param_source;
+	src.min_barcode_phred = _min_barcode_phred;
 	std::istringstream names(filenames);
 	std::string name;
-	const int quality_offset = 33;
 	while (names >> name) {
 		gzFile f = gzopen(name.c_str(), "rb");
 		if (!f) throw std::runtime_error("Can't open file with read parameters'" + name + "'");
-		std::string row;
-		char buf[1 << 16];
-		auto handle_row = [&]() {
-			if (row.empty()) return;
-			std::string parts[5];
-			size_t start = 0;
-			bool ok = true;
-			for (int i = 0; i < 4 && ok; ++i) {
-				const size_t end = row.find(' ', start);
-				if (end == std::string::npos) { ok = false; break; }
-				parts[i] = row.substr(start, end - start);
-				start = end + 1;
-			}
-			if (!ok) return;                                            // "can't parse read parameters from string": skipped
-			parts[4] = row.substr(start);
-			if (!parts[0].empty() && parts[0][0] == '@') parts[0] = parts[0].substr(1);
-			if (parts[1].empty() || parts[2].empty()) return;           // the ReadParameters constructor throws: skipped
-			bool pass = true;                                           // ReadParameters::check_quality (:118-136)
-			if (_min_barcode_phred > quality_offset) {
-				for (char q : parts[3]) pass &= q >= char(_min_barcode_phred);
-				for (char q : parts[4]) pass &= q >= char(_min_barcode_phred);
-			}
-			_read_params.emplace(parts[0], ReadParams{parts[1], parts[2], parts[4], pass});   // a repeated name keeps the first row
-		};
-		while (gzgets(f, buf, int(sizeof(buf)))) {
-			row += buf;
-			if (!row.empty() && row.back() == '\n') { row.pop_back(); if (!row.empty() && row.back() == '\r') row.pop_back(); handle_row(); row.clear(); }
+		(void)gzbuffer(f, 1u << 20);
+		const size_t begin = src.text.size();
+		for (;;) {
+			const size_t at = src.text.size(), chunk = size_t(8) << 20;
+			src.text.resize(at + chunk);
+			const int got = gzread(f, src.text.data() + at, unsigned(chunk));
+			src.text.resize(at + size_t(std::max(got, 0)));
+			if (got <= 0) break;
 		}
-		handle_row();
 		gzclose(f);
+		src.file_lines.push_back(src.lines());
+		const uint8_t *const p = src.text.data();
+		for (size_t at = begin, end = src.text.size(); at < end;) {
+			const void *nl = std::memchr(p + at, '\n', end - at);
+			const size_t next = nl ? size_t(static_cast<const uint8_t *>(nl) - p) + 1 : end;
+			src.line_be.push_back(at); src.line_be.push_back(next);
+			at = next;
+		}
 	}
+	src.file_lines.push_back(src.lines());
+}
+
+// The host reader's map, built when it first takes a file: malformed rows are skipped, a repeated name keeps its first row.  Rows that the
+// device path's table has served by then (files it took before this one) are consumed: they do not enter the map.
+void BamController::map_read_params() {
+	if (_read_params_mapped) return;
+	_read_params_mapped = true;
+	ParamSource &src = *_param_source;
+	const std::vector<uint8_t> consumed = consumed_read_params(src);
+	_read_params.reserve(src.lines());
+	ParamSource::Row r;
+	for (size_t k = 0; k < src.lines(); ++k) {
+		if (!src.row(k, r)) continue;      // "can't parse read parameters from string", or the ReadParameters constructor throws: skipped
+		const auto in = _read_params.emplace(std::string(r.name), ReadParams{std::string(r.cb), std::string(r.umi), std::string(r.umi_quality), r.pass});
+		if (in.second && !consumed.empty() && consumed[k]) in.first->second.cb.clear();      // (the first row of a name is the table's canonical one; dropped below)
+	}
+	if (!consumed.empty())
+		for (auto it = _read_params.begin(); it != _read_params.end();) { if (it->second.cb.empty()) it = _read_params.erase(it); else ++it; }
+	src.host_served = true;
+	if (!_device_read_sources) { std::vector<uint8_t>().swap(src.text); std::vector<uint64_t>().swap(src.line_be); }      // (nobody spells rows from the text any more)
 }
 
 // the workers: one record after the other of the worker's range parsed, counted and, if accepted, packed; what it brings new is noted
@@ -203,6 +215,7 @@ void BamController::add_record_by_record(FileIngest &file, const uint8_t *data, 
 
 // The host reader: BamReader inflates and finds the records, a window at a time
 void BamController::read_file_on_host(FileIngest &file, bool first_file) {
+	if (_params_from_files) map_read_params();
 	BamReader reader(file.bam_name, _threads);       // opened only when it is the one that reads (its loader thread inflates ahead from the start)
 	CellsDataContainer &container = file.container;
 	file.refs = reader.reference_names();
@@ -252,6 +265,8 @@ void BamController::parse_bam_files(const std::vector<std::string> &bam_files, b
 	join_release_thread();
 	for (auto const &bam_name : bam_files) {
 		FileIngest file(sw, bam_name, bam_files.size(), container, _counters, _tags, _filled_bam, _params_from_files, _gene_in_chromosome_name, _min_barcode_phred, _genes, nthreads);
+		file.device_sources = _device_read_sources && !print_result_bams;
+		if (file.device_sources && _params_from_files && !_param_source->host_served && !_param_source->text.empty()) file.params = _param_source.get();
 		struct NoteSaved { std::vector<size_t> &per_file; const Counters &c; size_t before; ~NoteSaved() { per_file.push_back(c.saved - before); } } note{_saved_per_file, _counters, _counters.saved};
 		if (print_result_bams) { _tagged.emplace_back(); file.tagged = &_tagged.back(); }
 		if (print_result_bams || _device_decode || sw.device) {

@@ -8,7 +8,10 @@
 // (a gene name, a chromosome, a string with N) are fetched as bytes and go through RecordParser + intern_new in file order,
 // exactly like the Needs of BulkWindow.  Windows grow from 1 MB of compressed bytes (the first ones meet most gene names).
 // Every block's CRC-32 is checked on the device (the wave that inflated it reads it back).  Falls back to the host reader (returns false before anything was added) when
-// the configuration needs what the kernels do not do: -r parameter files, gene = chromosome name.
+// the configuration needs what the kernels do not do: -r parameter files and gene = chromosome name unless BamController::set_device_read_sources
+// is on.  With it, -r is a table on the device (ParamSource::table_on; csrc/k_readparams.h) that every record's name is looked up in and that
+// serves each row once, to the first record of the stream that asks -- the decoder says which row each record was served, and the strings of the
+// few records the host must see are spelled from the row's line; -P is a table reference -> gene index (gene_of_reference_to_device).
 // Tagged BAM output (-b: parse_bam_files(files, true, container)) is made here and only here: every window's accepted records are edited on the device
 // (csrc/k_bamtag.h) before the window goes into the container, compressed there and written to `<input stem>.tagged.bam` (open_tagged, tag_window,
 // close_tagged); a file this path refuses is then an error that names the reason (FileIngest::refusal), not a file for the host reader.
@@ -69,6 +72,36 @@ void BamController::release_device_decoders() {
 	std::lock_guard<std::mutex> lk(decoder_cache_mutex());
 	for (auto &kv : decoder_cache()) dropest_bam_decoder_destroy(kv.second);
 	decoder_cache().clear();
+}
+
+// -r: the controller's rows as a table on `device` (made on first use; one table, on one GPU: the claims that make a row serve once live with it)
+dropest_read_params *ParamSource::table_on(int device) {
+	if (table) return device == table_device ? table : nullptr;
+	dropest_read_params *t = nullptr;
+	if (dropest_read_params_create(device, 0, &t)) return nullptr;
+	std::vector<uint64_t> off;
+	for (size_t f = 0; f + 1 < file_lines.size(); ++f) {      // a call per file: a file's last line ends with the file
+		const size_t l0 = size_t(file_lines[f]), l1 = size_t(file_lines[f + 1]);
+		if (l0 == l1) continue;
+		const uint64_t begin = line_be[2 * l0], end = line_be[2 * l1 - 1];
+		off.resize(l1 - l0);
+		for (size_t k = l0; k < l1; ++k) off[k - l0] = line_be[2 * k] - begin;
+		if (dropest_read_params_add_text(t, text.data() + begin, end - begin, off.data(), l1 - l0, min_barcode_phred)) { dropest_read_params_destroy(t); return nullptr; }
+	}
+	if (dropest_read_params_build(t)) { dropest_read_params_destroy(t); return nullptr; }
+	table = t; table_device = device;
+	return table;
+}
+ParamSource::~ParamSource() { if (table) dropest_read_params_destroy(table); }
+
+std::vector<uint8_t> consumed_read_params(ParamSource &src) {
+	std::vector<uint8_t> consumed;
+	if (!src.table) return consumed;
+	std::vector<uint64_t> claims(src.lines());
+	if (dropest_read_params_claims_to_host(src.table, 0, claims.size(), claims.data())) throw std::runtime_error(std::string("read parameters: ") + dropest_bgzf_last_error());
+	consumed.resize(claims.size());
+	for (size_t k = 0; k < claims.size(); ++k) consumed[k] = claims[k] != ~uint64_t(0);
+	return consumed;
 }
 
 // -F: what the files of one write_filtered_bam_files call share (bam_parse.h)
@@ -292,6 +325,8 @@ class DeviceFileReader {
 	std::vector<uint32_t> idx_all, offsets, p_pos, p_gene, p_aux; std::vector<uint64_t> need_off, p_cb, p_umi; std::vector<uint8_t> need_bytes;
 	std::vector<uint64_t> dict_hash; std::vector<uint32_t> dict_id; std::vector<int32_t> dict_chr;
 	std::vector<uint32_t> name_off; std::vector<uint8_t> name_pool;
+	std::vector<int32_t> gene_of_ref;      // -P: every reference's name in the gene dictionary (-1: not yet, -2: the name is empty)
+	std::vector<uint32_t> served;          // -r: the table row each asked record was served
 	double dev_ms[4] = {0, 0, 0, 0}, host_ms[3] = {0, 0, 0};
 	double ms_header = 0, ms_create = 0, ms_setup = 0, ms_wait_read = 0, ms_window_calls = 0;
 	size_t window_bytes = 0, n_windows = 0, repaired = 0, refused = 0, n_needs = 0, est_reads = 0;
@@ -346,6 +381,9 @@ class DeviceFileReader {
 		return stg;
 	}
 	void dictionaries_to_device();
+	void sources_to_decoder();
+	void gene_of_reference_to_device();
+	bool serve_row(uint32_t row, Parsed &pr) const;
 	void take_window(const dropest_bam_window &w, size_t used, clk::time_point t_call);
 	void records_through_host(const dropest_bam_window &w, size_t n);
 	void resolve_new(const dropest_bam_window &w);
@@ -441,7 +479,7 @@ bool DeviceFileReader::lease_decoder() {
 // (c) -g: the annotation's tables; false: positions beyond 32 bits, or no room for them (the host reader does it)
 bool DeviceFileReader::annotation_to_device() {
 	const std::vector<std::string> &refs = file.refs;
-	if (parser.genes.is_empty()) return true;
+	if (parser.genes.is_empty() || parser.gene_in_chromosome_name) return true;      // (-P comes before -g: the annotation is not asked)
 	try { flat = parser.genes.flatten(); } catch (const std::exception &) { return false; }   // (positions beyond 32 bits: the host reader does it)
 	dropest_flat_annotation fa{};
 	fa.n_chr = uint32_t(flat.chr_names.size()); fa.n_seg = uint32_t(flat.seg_start.size()); fa.n_tr = uint32_t(flat.tr_gene.size()); fa.n_genes = uint32_t(flat.gene_names.size());
@@ -758,9 +796,37 @@ void DeviceFileReader::dictionaries_to_device() {
 				if (id_of_ann_gene[g] < 0) id_of_ann_gene[g] = int32_t(container.lookup_gene(ann_gene_hash[g], flat.gene_names[g]));
 			if (dropest_bam_decoder_set_annotation_genes(dec, id_of_ann_gene.data(), uint32_t(id_of_ann_gene.size()))) fail();
 		}
+		if (parser.gene_in_chromosome_name) gene_of_reference_to_device();
 		dict_dirty = false;
 	}
 	host_ms[0] += since(t_phase);
+}
+
+// (c) -r: the controller's table, with the stream ordinal the file's first record claims with
+void DeviceFileReader::sources_to_decoder() {
+	if (file.params && dropest_bam_decoder_set_read_params(dec, file.params->table, file.params->ordinal)) fail();
+}
+
+// (f) -P: the references' names as the gene dictionary holds them by now
+void DeviceFileReader::gene_of_reference_to_device() {
+	const std::vector<std::string> &refs = file.refs;
+	gene_of_ref.resize(refs.size());
+	for (size_t r = 0; r < refs.size(); ++r) gene_of_ref[r] = refs[r].empty() ? -2 : int32_t(container.lookup_gene(CellsDataContainer::hash_name(refs[r]), refs[r]));
+	if (!refs.empty() && dropest_bam_decoder_set_gene_of_reference(dec, gene_of_ref.data(), uint32_t(refs.size()))) fail();
+}
+
+// (g) -r: what BamController::serve_read_params does with the map's entry, with the row the DEVICE served this record (RP: 0xFFFFFFFF = none):
+// no second look-up here.  false: the record is not to be looked at any further (it is counted under pr.status)
+bool DeviceFileReader::serve_row(uint32_t row, Parsed &pr) const {
+	if (pr.status == Parsed::SKIP || pr.status == Parsed::CANT_PARSE_NO_COUNT) return false;
+	ParamSource::Row r;
+	if (row == 0xFFFFFFFFu || row >= file.params->lines() || !file.params->row(row, r)) { pr.status = Parsed::CANT_PARSE; return false; }
+	if (!r.pass) { pr.status = Parsed::LOW_QUALITY; return false; }
+	if (pr.status != Parsed::OK) return false;
+	pr.r.cb = r.cb; pr.r.umi = r.umi; pr.r.umi_quality = r.umi_quality; pr.r.umi_quality_length = uint32_t(r.umi_quality.size());
+	if (!CellsDataContainer::pack_code(pr.r.cb, pr.r.cb_code)) pr.r.cb_code = 0;
+	if (!CellsDataContainer::pack_code(pr.r.umi, pr.r.umi_code)) pr.r.umi_code = 0;
+	return true;
 }
 
 // (g) UMI quality strings the container cannot take in bulk (it keeps them on the host): the records of this window come back as bytes and
@@ -774,10 +840,13 @@ void DeviceFileReader::records_through_host(const dropest_bam_window &w, size_t 
 	offsets.resize(n);
 	for (size_t i = 0; i < n; ++i) offsets[i] = uint32_t(need_off[i]);
 	dict_dirty = true;
-	if (w.window_bytes < (uint64_t(1) << 32) && !sw.record_by_record && container.bulk_ingest_possible_at_all() && file.bulk.ingest(need_bytes.data(), offsets, n)) return;
+	// (-r: record by record, as the host reader goes under -r; every record with the row the device served it)
+	if (!file.params && w.window_bytes < (uint64_t(1) << 32) && !sw.record_by_record && container.bulk_ingest_possible_at_all() && file.bulk.ingest(need_bytes.data(), offsets, n)) return;
+	if (file.params) { served.resize(n); if (dropest_bam_decoder_param_rows(dec, nullptr, uint32_t(n), served.data())) fail(); }
 	Parsed tmp;
 	for (size_t i = 0; i < n; ++i) {
 		parser.parse(need_bytes.data() + need_off[i], tmp);
+		if (file.params) serve_row(served[i], tmp);
 		if (count_status(file.counters, tmp.status)) container.add_record(tmp.r);
 	}
 }
@@ -791,9 +860,11 @@ void DeviceFileReader::resolve_new(const dropest_bam_window &w) {
 	need_bytes.resize(bytes + 16); need_off.resize(m);
 	p_pos.resize(m); p_cb.resize(m); p_umi.resize(m); p_gene.resize(m); p_aux.resize(m);
 	if (dropest_bam_decoder_fetch_records(dec, w.need_rec, uint32_t(m), need_bytes.data(), need_bytes.size(), need_off.data())) fail();
+	if (file.params) { served.resize(m); if (dropest_bam_decoder_param_rows(dec, w.need_rec, uint32_t(m), served.data())) fail(); }
 	Parsed tmp;
 	for (size_t k = 0; k < m; ++k) {
 		parser.parse(need_bytes.data() + need_off[k], tmp);
+		if (file.params) serve_row(served[k], tmp);      // (-r: barcode, UMI and quality of the row the device served; -P: the parser names the reference itself)
 		if (tmp.status != Parsed::OK) throw std::runtime_error("internal: the device and the host read a BAM record differently: " + file.bam_name);
 		const CellsDataContainer::ParsedRead &r = tmp.r;
 		const bool has_gene = !r.gene.empty();
@@ -811,6 +882,7 @@ void DeviceFileReader::resolve_new(const dropest_bam_window &w) {
 // (g) one decoded window into the container and the counters
 void DeviceFileReader::take_window(const dropest_bam_window &w, size_t used, clk::time_point t_call) {
 	ms_window_calls += since(t_call);
+	if (file.params) file.params->ordinal += w.n_records;      // (the next file's first record claims above every record of this one)
 	if (file.filtered) { first = false; ++n_windows; filter_window(w); return; }      // the second pass: nothing goes into the container
 	if (file.tagged) tag_window(w);      // first thing: whichever way the window then goes into the container, its accepted records are written
 	if (first) {
@@ -910,6 +982,7 @@ bool DeviceFileReader::read() {
 	if (!lease_decoder()) { file.refusal = std::string("no GPU decoder (") + dropest_bgzf_last_error() + ")"; return false; }
 	ms_create = since(t_enter) - ms_header;
 	if (!annotation_to_device()) { file.refusal = "the gene annotation cannot be held on the device"; return false; }
+	sources_to_decoder();
 	if (file.tagged) open_tagged();
 	if (file.filtered) open_filtered();
 	t_file = clk::now();
@@ -925,6 +998,7 @@ bool DeviceFileReader::read() {
 	if (sw.pipeline) windows_pipelined(); else windows_one_by_one();
 	if (file.tagged) close_tagged();
 	if (file.filtered) close_filtered();
+	if (file.params) (void)dropest_bam_decoder_set_read_params(dec, nullptr, 0);      // (the decoder may be kept longer than the controller's table lives)
 	sw.trace("[bam] device path: %zu windows, %.1f ms behind the header; copy in %.1f ms, inflate %.1f ms (%zu blocks left to the host), record chain %.1f ms (%zu guesses "
 	         "repaired), fields + dense columns %.1f ms; host: dictionaries to the device %.1f ms, %zu records with something new %.1f ms, container %.1f ms\n",
 	         n_windows, since(t_file), dev_ms[0], dev_ms[1], refused, dev_ms[2], repaired, dev_ms[3], host_ms[0], n_needs, host_ms[1], host_ms[2]);
@@ -939,8 +1013,9 @@ bool DeviceFileReader::read() {
 
 bool read_file_on_device(FileIngest &file) {
 	const RecordParser &parser = file.parser;
-	if (parser.params_from_files) { file.refusal = "read-parameter files (-r) are served by the host reader"; return false; }
-	if (parser.gene_in_chromosome_name) { file.refusal = "gene = chromosome name is resolved by the host reader"; return false; }
+	const bool output = file.tagged || file.filtered;      // (-b and -F under -r or -P: the tag kernels would need the row's strings and the chromosome's name)
+	if (parser.params_from_files && (!file.params || output)) { file.refusal = "read-parameter files (-r) are served by the host reader"; return false; }
+	if (parser.gene_in_chromosome_name && (!file.device_sources || output)) { file.refusal = "gene = chromosome name is resolved by the host reader"; return false; }
 	// (-b stays here whatever the container takes: a window it cannot take in bulk goes through records_through_host, record by record if need be)
 	if (!file.tagged && !file.filtered && !file.container.bulk_ingest_possible_at_all(true)) { file.refusal = "the container no longer takes reads in bulk"; return false; }
 	CellsDataContainer::IngestTarget target = file.container.next_read_target();
@@ -951,6 +1026,9 @@ bool read_file_on_device(FileIngest &file) {
 	}
 	const auto t_enter = clk::now();
 	if (parser.tags.intronic_read_value.size() > 24 || parser.tags.intergenic_read_value.size() > 24) { file.refusal = "a read-type value is longer than 24 bytes"; return false; }
+	// -r: the table on the GPU this file's decoder will sit on (a container over several GPUs may want another one than the table's: the claims
+	// would have to be carried over -- the host reader takes the file instead)
+	if (file.params && !file.params->table_on(target.device)) { file.refusal = "the read-parameter table cannot be held on this file's GPU"; return false; }
 	DeviceFileReader reader(file, target, t_enter);
 	return reader.read();
 }

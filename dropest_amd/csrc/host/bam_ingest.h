@@ -19,6 +19,7 @@
 #pragma once
 
 #include <cstdint>
+#include <memory>
 #include <string>
 #include <unordered_map>
 #include <string_view>
@@ -102,9 +103,13 @@ public:
 private:
 	BamTags _tags;
 	struct ReadParams { std::string cb, umi, umi_quality; bool pass_quality; };
-	std::unordered_map<std::string, ReadParams> _read_params;     // -r: read name -> parameters (erased when served)
+	std::unordered_map<std::string, ReadParams> _read_params;     // -r: read name -> parameters (erased when served); built when the host reader first takes a file
 	bool _params_from_files = false;
+	std::shared_ptr<struct ParamSource> _param_source;            // -r: the files' inflated text and, on the device path, its table (bam_parse.h)
+	bool _read_params_mapped = false;
+	bool _device_read_sources = false;
 	void load_read_params(const std::string &filenames);
+	void map_read_params();
 	void serve_read_params(Parsed &pr);
 	void add_record_by_record(FileIngest &file, const uint8_t *data, const std::vector<uint32_t> &offsets, std::vector<Parsed> &parsed);
 	void read_file_on_host(FileIngest &file, bool first_file);
@@ -153,10 +158,18 @@ public:
 	void set_sharded_filtered_output(bool on) { _sharded_filtered_output = on; }
 	const FilteredFile &filtered_file() const { return _filtered; }           // of the last write_filtered_bam_files call (empty when it threw)
 	// BGZF inflate, record chain and tag walk on the container's GPU (include/dropest_bgzf.h) where the configuration allows it: tags or read
-	// names as the source of barcode / UMI, the gene tag or a -g annotation (annotation_api.hip) as the source of the gene; not with -r or gene =
-	// chromosome name (the host reader then runs).  A sharded container is fed by one decoder on the GPU of the shard the file's first read goes to.
+	// names as the source of barcode / UMI, the gene tag or a -g annotation (annotation_api.hip) as the source of the gene; with -r or gene =
+	// chromosome name only behind set_device_read_sources (otherwise the host reader runs).  A sharded container is fed by one decoder on the GPU of the shard the file's first read goes to.
 	// CRC-32 and ISIZE of every block are checked there too.  DROPEST_BAM_DEVICE=1 in the environment does the same.
 	void set_device_decode(bool on) { _device_decode = on; }
+	// The device BAM path also takes files under -r (read-parameter files) and -P (gene = chromosome name) for INGEST (off by default: such files
+	// go to the host reader, as before).  -r: the files' rows become a table on the container's GPU (include/dropest_bgzf.h:
+	// dropest_read_params_*), probed by every record's name there, each row serving the first record of the stream that asks, as the host
+	// reader's map does; -P: the reference's name is the gene, a constant per record.  The answer is the host reader's.  Tagged and filtered
+	// output (-b, -F) under -r or -P stay refused either way.  A file the device path cannot take after all (no GPU, a container over several
+	// GPUs whose next read lives on another GPU than the table) goes to the host reader with the rows the device served taken out of its map;
+	// from then on the host reader serves every later file.  DESIGN.md section 7.
+	void set_device_read_sources(bool on) { _device_read_sources = on; }
 	// the device path keeps one decoder per GPU (streams, 2-7 GB of device buffers, up to 512 MB of pinned staging) between the files of one
 	// parse_bam_files call; they are given back on a helper thread when the call ends (DROPEST_BAM_KEEP_DECODERS=1: kept for the next call).
 	// This waits for that thread and frees whatever is still cached.

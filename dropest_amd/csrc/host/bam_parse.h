@@ -17,6 +17,8 @@
 #include <stdexcept>
 #include <thread>
 
+struct dropest_read_params;      // include/dropest_bgzf.h: the read-parameter table on the device
+
 namespace Estimation {
 namespace BamProcessing {
 
@@ -128,6 +130,45 @@ struct Parsed {
 	CellsDataContainer::ParsedRead r; uint8_t status; std::string gene; /* -g: the annotation's answer (owned) */
 	std::string_view name;                  // -r: the read name, looked up in file order by the caller's thread
 	std::string p_cb, p_umi, p_quality;     // -r: the served parameters (owned: the map entry is erased)
+};
+
+// -r: the read-parameter files as the controller keeps them -- the inflated text of every file, one after the other, and the two ends of every
+// line in it (a line's '\n' included; a file's last line may have none).  Nothing is split and no map is built here: the host reader builds its
+// map from the lines when it first takes a file (BamController::map_read_params), the device path makes a table on the container's GPU
+// (include/dropest_bgzf.h: dropest_read_params_*; table_on, bam_device.cpp) and spells a served row's strings from its line (row k = line k).
+struct ParamSource {
+	std::vector<uint8_t> text;
+	std::vector<uint64_t> line_be;              // line k: text[line_be[2 k] .. line_be[2 k + 1])
+	std::vector<uint64_t> file_lines;           // the first line of every file, and the number of lines behind the last
+	int min_barcode_phred = 0;
+	dropest_read_params *table = nullptr;       // on GPU table_device, made when the device path first takes a file; its claims live as long as this
+	int table_device = -1;
+	uint64_t ordinal = 0;                       // records the device path has been through: the next window's first record claims with this
+	bool host_served = false;                   // the host reader's map has served rows the table does not know of: no more files for the device path
+	~ParamSource();
+	dropest_read_params *table_on(int device);  // null: no table on that GPU (none can be made, or the table lives on another one)
+	struct Row { std::string_view name, cb, umi, cb_quality, umi_quality; bool pass; };
+	// BamController::load_read_params' row rules (ReadParameters::parse_from_string, check_quality); false: the line gives no row
+	bool row(size_t k, Row &out) const {
+		const char *b = reinterpret_cast<const char *>(text.data()) + line_be[2 * k], *e = reinterpret_cast<const char *>(text.data()) + line_be[2 * k + 1];
+		if (e > b && e[-1] == '\n') { --e; if (e > b && e[-1] == '\r') --e; }
+		std::string_view rest(b, size_t(e - b)), part[5];
+		for (int i = 0; i < 4; ++i) {
+			const size_t sp = rest.find(' ');
+			if (sp == std::string_view::npos) return false;
+			part[i] = rest.substr(0, sp); rest.remove_prefix(sp + 1);
+		}
+		part[4] = rest;
+		if (!part[0].empty() && part[0][0] == '@') part[0].remove_prefix(1);
+		if (part[1].empty() || part[2].empty()) return false;
+		out = Row{part[0], part[1], part[2], part[3], part[4], true};
+		if (min_barcode_phred > 33) {
+			for (char q : part[3]) out.pass &= q >= char(min_barcode_phred);
+			for (char q : part[4]) out.pass &= q >= char(min_barcode_phred);
+		}
+		return true;
+	}
+	size_t lines() const { return line_be.size() / 2; }
 };
 
 // A parse status into the counters (BamController::Counters, or a worker's tally with the same members); true: the record is to be saved.
@@ -301,6 +342,8 @@ struct FileIngest {
 	BamController::TaggedFile *tagged = nullptr;   // -b: this file's tagged BAM is to be written (device path only); what was written is noted here
 	struct FilteredPass *filtered = nullptr;       // -F: the file is read for write_filtered_bam_files -- nothing goes into the container
 	std::string refusal;                 // why the device path handed the file back (read_file_on_device returned false)
+	bool device_sources = false;         // BamController::set_device_read_sources: the device path may take the file under -r and -P (ingest only)
+	ParamSource *params = nullptr;       // -r with that switch: the rows for the device path's table
 	FileIngest(const BamSwitches &sw, const std::string &bam_name, size_t n_files, CellsDataContainer &container, BamController::Counters &counters,
 	           const BamTags &tags, bool filled_bam, bool params_from_files, bool gene_in_chromosome_name, int min_barcode_phred,
 	           const Tools::GeneAnnotation::RefGenesContainer &genes, unsigned threads)
@@ -322,6 +365,8 @@ uint64_t filtered_pass_total(const FilteredPass *pass);      // the container's 
 
 // bam_device.cpp: the file through the GPU (include/dropest_bgzf.h); false: the host reader is to read it, nothing was added
 bool read_file_on_device(FileIngest &file);
+// -r: per line of src, whether the device path's table served it (empty: there is no table, nothing was served)
+std::vector<uint8_t> consumed_read_params(ParamSource &src);
 void join_release_thread();
 void release_decoders_in_background();
 

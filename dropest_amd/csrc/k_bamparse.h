@@ -19,6 +19,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "k_readparams.h"
+
 namespace dropest {
 
 constexpr uint32_t BAM_SEG = 16384;
@@ -163,13 +165,30 @@ __device__ inline bool bam_equal(const uint8_t *a, uint32_t n, const uint8_t *b,
 	return true;
 }
 
+// The two sources beside the record's own tags and name (dropest_bam_decoder_set_read_params / _set_gene_of_reference):
+//   -r  (BAM_SRC_PARAMS): barcode, UMI and UMI quality come from the read-parameter table (k_readparams.h) by the read's name.  The parse only
+//       looks the name up and claims the row with the record's ordinal in the stream (first_ordinal + its index in the window: ascending in file
+//       order); bam_params_settle_kernel, a launch of its own, then serves the record whose ordinal stands in the claim -- the reference erases a
+//       served name from its map (ReadMapParamsParser.cpp:22-48), so the first record of the file order is the one that gets the row.
+//   -P  (BAM_SRC_REF_GENE): the gene is the reference's name (ReadParamsParser.cpp:42-48), a constant per record: gene_of_ref[ref] = its index
+//       in the host's gene dictionary, -1 = not interned yet (a need record), -2 = an empty name (no gene, mark 0).
+enum : int { BAM_SRC_PARAMS = 1, BAM_SRC_REF_GENE = 2 };
+constexpr unsigned long long BAM_Q_IN_TABLE = 1ull << 63;      // qoff: the UMI quality string stands in the table's text, not in the window
+struct BamSources {
+	RpTable table;
+	unsigned long long first_ordinal;      // of the window's first record
+	uint32_t *rp_row;                      // per record: the row it found (after the settle: the row it was served, RP_NONE otherwise)
+	const int32_t *gene_of_ref;
+};
+
 // One lane per record (host/bam_ingest.cpp: parse_one, the branches that need no dictionary).
 // The 64 records of a wave follow one another in the stream (~17 KB of a 10x BAM): the wave copies them into LDS with coalesced 16-byte loads
 // and every lane walks ITS record there -- the walk is ~150 loads of single bytes per record, and from memory each of them is 64 transactions
 // per wave (the records lie 270 bytes apart), which is what bounded the kernel.  Records that do not fit the wave's 20 KB are walked in memory.
+// SRC: the BAM_SRC_* bits; 0 is the kernel as it was before there were any (bam_parse_kernel, whose code does not change with them).
 constexpr uint32_t BAM_PARSE_T = 128, BAM_PARSE_STAGE = 20480;
-__global__ __launch_bounds__(BAM_PARSE_T) void bam_parse_kernel(const uint8_t *__restrict__ d, const uint64_t *__restrict__ rec_off, uint32_t n_rec, BamParseCfg cfg,
-                                                                BamDict dict, BamRecordOut out, uint32_t *__restrict__ bad) {
+template <int SRC> __device__ __forceinline__ void bam_parse_records(const uint8_t *__restrict__ d, const uint64_t *__restrict__ rec_off, uint32_t n_rec, const BamParseCfg &cfg,
+                                                                     const BamDict &dict, const BamRecordOut &out, uint32_t *__restrict__ bad, const BamSources &src) {
 	__shared__ __attribute__((aligned(16))) uint8_t stage[BAM_PARSE_T / 64][BAM_PARSE_STAGE];
 	const uint32_t i = blockIdx.x * BAM_PARSE_T + threadIdx.x;
 	const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
@@ -197,10 +216,19 @@ __global__ __launch_bounds__(BAM_PARSE_T) void bam_parse_kernel(const uint8_t *_
 	const int32_t ref_id = int32_t(b_le32(p));
 	const uint32_t l_read_name = p[8], n_cigar = b_le16(p + 12), flag = b_le16(p + 14), l_seq = b_le32(p + 16);
 	out.umiq_len[i] = 0; out.need[i] = 0; out.qoff[i] = ~0ull;
+	if constexpr (SRC & BAM_SRC_PARAMS) src.rp_row[i] = RP_NONE;
 	const uint64_t aux = 32ull + l_read_name + 4ull * n_cigar + (uint64_t(l_seq) + 1) / 2 + l_seq;
 	if (aux > block_size) { out.status[i] = BAM_CANT_PARSE; atomicOr(bad, 1u); return; }   // the host reader throws "Corrupt BAM record" (host/bam_ingest.cpp parse_one): so does the window, from this flag
 	if ((flag & 0x4u) || (flag & 0x100u)) { out.status[i] = BAM_SKIP; return; }                    // BamController.cpp:87-88
 	if (ref_id < 0 || ref_id >= cfg.n_refs) { out.status[i] = BAM_CANT_PARSE_NO_COUNT; return; }  // :90-104
+	if constexpr (SRC & BAM_SRC_PARAMS) {      // the name (one '@' off, BamController::serve_read_params) claims its row; who is served: bam_params_settle_kernel
+		const uint8_t *name = p + 32;
+		uint32_t nl = l_read_name ? l_read_name - 1 : 0;
+		if (nl && name[0] == '@') { ++name; --nl; }
+		const uint32_t row = rp_lookup(src.table, name, nl);
+		src.rp_row[i] = row;
+		if (row != RP_NONE) atomicMin(&src.table.claim[row], src.first_ordinal + i);
+	}
 	// the tags asked for, in one walk (BamRecord::get_string_tags)
 	const uint8_t *tags = p + aux;
 	const uint32_t tags_size = block_size - uint32_t(aux);
@@ -249,7 +277,8 @@ __global__ __launch_bounds__(BAM_PARSE_T) void bam_parse_kernel(const uint8_t *_
 	const uint8_t *cb = nullptr, *umi = nullptr;
 	uint32_t cb_n = 0, umi_n = 0;
 	bool pass = true;
-	if (cfg.filled_bam) {                                                     // FilledBamParamsParser.cpp:12-40
+	if constexpr (SRC & BAM_SRC_PARAMS) {}                                    // (the settle brings barcode, UMI and the quality verdict)
+	else if (cfg.filled_bam) {                                                // FilledBamParamsParser.cpp:12-40
 		if (!found[T_CB] || !found[T_UMI]) { out.status[i] = BAM_CANT_PARSE; return; }
 		cb = val[T_CB]; cb_n = vlen[T_CB]; umi = val[T_UMI]; umi_n = vlen[T_UMI];
 		if (!cb_n || !umi_n) { out.status[i] = BAM_CANT_PARSE; return; }
@@ -270,7 +299,7 @@ __global__ __launch_bounds__(BAM_PARSE_T) void bam_parse_kernel(const uint8_t *_
 		if (!cb_n || !umi_n) { out.status[i] = BAM_CANT_PARSE; return; }
 	}
 	if (!pass) { out.status[i] = BAM_LOW_QUALITY; return; }
-	if (dict.ann_chr_of_ref) {                                                // -g: the gene comes from the alignment's place (bam_resolve_annotated)
+	if (!(SRC & BAM_SRC_REF_GENE) && dict.ann_chr_of_ref) {                   // -g: the gene comes from the alignment's place (bam_resolve_annotated)
 		int64_t ref_len = 0;                                                  // BamAlignment::GetEndPosition: reference bases of M, D, N, =, X
 		const uint8_t *cig = p + 32 + l_read_name;
 		for (uint32_t k = 0; k < n_cigar; ++k) {
@@ -287,7 +316,9 @@ __global__ __launch_bounds__(BAM_PARSE_T) void bam_parse_kernel(const uint8_t *_
 	}
 	uint32_t mark;                                                            // get_gene + parse_read_type (ReadParamsParser.cpp:36-90)
 	unsigned long long gh = 0;
-	if (!found[T_GENE]) mark = 1;                                             // HAS_NOT_ANNOTATED
+	int32_t ref_gene = -2;
+	if constexpr (SRC & BAM_SRC_REF_GENE) { ref_gene = src.gene_of_ref[ref_id]; mark = ref_gene == -2 ? 0u : 2u; }   // -P: before -g and the gene tag; HAS_EXONS unless the name is empty
+	else if (!found[T_GENE]) mark = 1;                                        // HAS_NOT_ANNOTATED
 	else {
 		if (vlen[T_GENE]) {
 			gh = 1469598103934665603ull;                                      // FNV-1a, as CellsDataContainer::hash_name
@@ -300,24 +331,25 @@ __global__ __launch_bounds__(BAM_PARSE_T) void bam_parse_kernel(const uint8_t *_
 		else mark = 2;
 	}
 	// the columns of dropest_push_reads, as fast_window of host/bam_ingest.cpp fills them
-	const bool has_gene = found[T_GENE] && vlen[T_GENE];
+	const bool has_gene = (SRC & BAM_SRC_REF_GENE) ? ref_gene != -2 : found[T_GENE] && vlen[T_GENE];
 	bool need = false;
-	const unsigned long long cbc = bam_pack_bases(cb, cb_n);
-	need |= !cbc;
+	const unsigned long long cbc = bam_pack_bases(cb, cb_n);                  // (-r: of nothing, 0 -- the settle brings the code and what it means for `need`)
+	if constexpr (!(SRC & BAM_SRC_PARAMS)) need |= !cbc;
 	unsigned long long uc = 1;
 	uint32_t gid = 0xFFFFFFFFu;                                               // DROPEST_NO_GENE
 	if (has_gene) {
 		uc = bam_pack_bases(umi, umi_n);
-		need |= !uc;
+		if constexpr (!(SRC & BAM_SRC_PARAMS)) need |= !uc;
 		uint32_t sl = bam_dict_slot(gh, dict.gmask);
 		gid = 0;
-		for (;;) {
+		if constexpr (SRC & BAM_SRC_REF_GENE) { if (ref_gene < 0) need = true; else gid = uint32_t(ref_gene); }
+		else for (;;) {
 			const uint32_t v = dict.gvals[sl];
 			if (!v) { need = true; break; }
 			if (dict.gkeys[sl] == gh) { gid = v - 1; break; }
 			sl = (sl + 1) & dict.gmask;
 		}
-		if (!need && dict.name_off) {      // the name behind the hash, byte by byte ("exact only with probability" otherwise)
+		if (!(SRC & BAM_SRC_REF_GENE) && !need && dict.name_off) {      // the name behind the hash, byte by byte ("exact only with probability" otherwise)
 			bool same = gid < dict.n_names;
 			if (same) {
 				const uint32_t o = dict.name_off[gid], nlen = dict.name_off[gid + 1] - o;
@@ -335,6 +367,36 @@ __global__ __launch_bounds__(BAM_PARSE_T) void bam_parse_kernel(const uint8_t *_
 	out.cb[i] = cbc; out.umi[i] = uc; out.gene[i] = gid; out.aux[i] = aux_w;
 	out.need[i] = need ? (has_gene ? 3 : 1) : (has_gene ? 2 : 0);             // bit 0: the host must see the record; bit 1: it carries a gene
 	out.status[i] = BAM_OK;
+}
+
+__global__ __launch_bounds__(BAM_PARSE_T) void bam_parse_kernel(const uint8_t *__restrict__ d, const uint64_t *__restrict__ rec_off, uint32_t n_rec, BamParseCfg cfg,
+                                                                BamDict dict, BamRecordOut out, uint32_t *__restrict__ bad) {
+	bam_parse_records<0>(d, rec_off, n_rec, cfg, dict, out, bad, BamSources{});
+}
+template <int SRC> __global__ __launch_bounds__(BAM_PARSE_T) void bam_parse_sources_kernel(const uint8_t *__restrict__ d, const uint64_t *__restrict__ rec_off, uint32_t n_rec, BamParseCfg cfg,
+                                                                                           BamDict dict, BamRecordOut out, uint32_t *__restrict__ bad, BamSources src) {
+	bam_parse_records<SRC>(d, rec_off, n_rec, cfg, dict, out, bad, src);
+}
+
+// -r, behind the parse in a launch of its own (so that every claim of the window, and of the windows before it, is made): an accepted record is
+// served when its ordinal is the one that stands in its row's claim (BamController::serve_read_params).  No row, or a row that an earlier
+// record took: "can't parse".  A row that fails the quality filter is taken all the same and the record is "low quality" -- before the gene is
+// asked for, so under -g this wins over a chromosome the annotation lacks (which, decided later by bam_resolve_annotated, still took its row).
+// Otherwise the row's codes and quality string become the record's; annotated (-g): bam_resolve_annotated finishes `need` from the codes.
+__global__ __launch_bounds__(256) void bam_params_settle_kernel(uint32_t n_rec, BamSources src, BamRecordOut out, int annotated) {
+	const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+	if (i >= n_rec || out.status[i] != BAM_OK) return;
+	const uint32_t row = src.rp_row[i];
+	if (row == RP_NONE || src.table.claim[row] != src.first_ordinal + i) { src.rp_row[i] = RP_NONE; out.status[i] = BAM_CANT_PARSE; return; }
+	const RpRow r = src.table.rows[row];
+	if (!r.pass) { out.status[i] = BAM_LOW_QUALITY; return; }
+	out.umiq_len[i] = r.quality_len; out.qoff[i] = BAM_Q_IN_TABLE | r.quality_off;
+	out.cb[i] = r.cb_code; out.umi[i] = r.umi_code;
+	if (annotated) return;
+	const uint8_t nd = out.need[i];
+	const bool has_gene = nd & 2u;
+	if (!has_gene) out.umi[i] = 1;
+	if (!r.cb_code || (has_gene && !r.umi_code)) out.need[i] = nd | 1u;
 }
 
 // -g: what annotate_reads (annotation_api.hip) said about the accepted records -> the columns (host/bam_ingest.cpp parse_one, the -g branch)
@@ -463,14 +525,15 @@ __global__ __launch_bounds__(256) void bam_fin_scatter_kernel(const uint8_t *__r
 
 // one row of ql bytes per accepted read: its UMI quality string (zeros for a read without a gene or without a string); the caller has seen that
 // every gene-bearing read's string is ql long
-__global__ __launch_bounds__(256) void bam_quality_rows_kernel(const uint8_t *__restrict__ d, const unsigned long long *__restrict__ qoff, uint32_t n, uint32_t ql,
-                                                               uint8_t *__restrict__ rows) {
+// (-r: a string marked BAM_Q_IN_TABLE stands in the read-parameter table's text)
+__global__ __launch_bounds__(256) void bam_quality_rows_kernel(const uint8_t *__restrict__ d, const uint8_t *__restrict__ table_text, const unsigned long long *__restrict__ qoff,
+                                                               uint32_t n, uint32_t ql, uint8_t *__restrict__ rows) {
 	const uint32_t k = blockIdx.x * 256 + threadIdx.x;
 	if (k >= n) return;
 	const unsigned long long o = qoff[k];
 	uint8_t *row = rows + size_t(k) * ql;
 	if (o == ~0ull) { for (uint32_t j = 0; j < ql; ++j) row[j] = 0; }
-	else { const uint8_t *q = d + o; for (uint32_t j = 0; j < ql; ++j) row[j] = q[j]; }
+	else { const uint8_t *q = (o & BAM_Q_IN_TABLE) ? table_text + (o & ~BAM_Q_IN_TABLE) : d + o; for (uint32_t j = 0; j < ql; ++j) row[j] = q[j]; }
 }
 
 // what the host resolved (new dictionary entries, strings with N) back into the dense columns

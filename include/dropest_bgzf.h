@@ -157,6 +157,53 @@ int dropest_bam_decoder_quality_rows(dropest_bam_decoder *d, uint32_t ql, const 
 int dropest_bam_decoder_patch(dropest_bam_decoder *d, const uint32_t *pos, const uint64_t *cb, const uint64_t *umi, const uint32_t *gene,
                               const uint32_t *aux, uint32_t n);
 
+/* ---- -r: read-parameter files as a table on the device (csrc/k_readparams.h, csrc/bam_read_params.h; DESIGN.md section 7 has the rules) ---------------
+ * What ReadMapParamsParser (ReadMapParamsParser.cpp:22-108) keeps in an unordered_map: read name -> barcode, UMI, UMI quality, quality verdict, each
+ * name serving ONE record, the first of the file order that asks.  The caller inflates the gzip files and finds the line starts; the rows are
+ * validated, packed, hashed and entered on the device.  An object of its own: decoders come and go per file, the table and its claims stay.  Every
+ * call returns with its work done; none may run while a window of a decoder that was given the table is in flight. */
+typedef struct dropest_read_params dropest_read_params;
+typedef struct dropest_read_params_row {   /* one line of the files; offsets into the table's text = the bytes of every _add_text call, one after the other */
+	uint64_t hash;                         /* FNV-1a 64 of the name (under the table's hash mask) */
+	uint64_t cb_code, umi_code;            /* packed codes of dropest_amd.h; 0 = does not pack (an N, more than 31 bases): the caller spells it from the text */
+	uint64_t name_off, cb_off, umi_off, quality_off;      /* the name without its '@'; the UMI quality is the fifth field, the rest of the line */
+	uint32_t name_len, cb_len, umi_len, quality_len;
+	uint32_t canonical;                    /* the first row that carries this name (the row itself when it is that one): the row look-ups answer with; 0xFFFFFFFF when !valid */
+	uint8_t valid, pass, empty, pad;       /* valid: five fields, barcode and UMI not empty; pass: the quality verdict; empty: the line has no character */
+} dropest_read_params_row;
+/* hash_bits in 1 .. 63: only that many bits of a name's hash are used (tests: names that collide); anything else: all 64. */
+int dropest_read_params_create(int device, int hash_bits, dropest_read_params **out);
+/* text[0 .. len): lines of "name cb umi cb_quality umi_quality"; line k begins at line_off[k] and ends where line k + 1 begins (the last one at len),
+ * its '\n' included if it has one.  min_phred as in dropest_bam_parse_cfg.  Callable several times before _build (one call per file, say): row
+ * numbers go on counting, and a name met again keeps its FIRST row, across calls too.  The text is copied. */
+int dropest_read_params_add_text(dropest_read_params *t, const uint8_t *text, uint64_t len, const uint64_t *line_off, uint64_t n_lines, int min_phred);
+int dropest_read_params_build(dropest_read_params *t);      /* once; the table is of the power of two >= 2 x rows (at least 64) slots */
+/* rows: lines; valid; malformed: neither valid nor empty; repeated: valid rows whose name an earlier row carries.  Any pointer may be NULL. */
+int dropest_read_params_counts(dropest_read_params *t, uint64_t *rows, uint64_t *valid, uint64_t *malformed, uint64_t *repeated);
+int dropest_read_params_rows_to_host(dropest_read_params *t, uint64_t first, uint64_t n, dropest_read_params_row *out);
+/* name k = name_pool[name_off[k] .. name_off[k + 1]) (n + 1 offsets; one '@' in front is passed over, as for a record's name) -> out_row[k] = its
+ * canonical row, 0xFFFFFFFF = not listed.  The device function the decoder's parse kernel calls, a lane per name.  Claims nothing. */
+int dropest_read_params_lookup(dropest_read_params *t, const uint8_t *name_pool, const uint64_t *name_off, uint64_t n, uint32_t *out_row);
+/* claim[row]: the lowest stream ordinal among the records that found the row (dropest_bam_decoder_set_read_params), all ones = none did: a row with
+ * a claim is consumed, for the table's life or until _reset_claims. */
+int dropest_read_params_claims_to_host(dropest_read_params *t, uint64_t first, uint64_t n, uint64_t *out);
+int dropest_read_params_reset_claims(dropest_read_params *t);
+void dropest_read_params_destroy(dropest_read_params *t);
+/* The decoder takes barcode, UMI and UMI quality of every record from `table` (same GPU; stays the caller's) by the read's name, one '@' off.  A
+ * record that is neither skipped nor on an unknown reference claims the row it finds with its stream ordinal: first_ordinal + the records of the
+ * windows finished since this call + its index in the window.  A launch behind the parse serves the record whose ordinal stands in the claim: no
+ * row, or a row claimed by an earlier record -> DROPEST_BAM_CANT_PARSE; a row that fails the quality filter -> DROPEST_BAM_LOW_QUALITY (the row is
+ * taken all the same); else the row's codes and quality string are the record's (a code of 0 makes it a need record).  first_ordinal must lie above
+ * every ordinal that claimed a row of the table before.  NULL turns it off, as a reset does.  Refused under -f and with tagged output. */
+int dropest_bam_decoder_set_read_params(dropest_bam_decoder *d, dropest_read_params *table, uint64_t first_ordinal);
+/* -P (gene = chromosome name, ReadParamsParser.cpp:42-48): gene_of_ref[r] = index of reference r's name in the caller's gene dictionary, -1 = not in
+ * it yet (a record on r is a need record; send the table again once the dictionary has grown), -2 = the name is empty (no gene, mark 0).  Other
+ * records carry mark HAS_EXONS.  Comes before an annotation and the gene tag; the read type is not looked at.  NULL turns it off, as a reset does. */
+int dropest_bam_decoder_set_gene_of_reference(dropest_bam_decoder *d, const int32_t *gene_of_ref, uint32_t n_refs);
+/* For records rec_idx[0 .. n) of the LAST window (NULL: its first n records): the row of the table each was served (a row that fails the quality
+ * filter included), 0xFFFFFFFF for every other record. */
+int dropest_bam_decoder_param_rows(dropest_bam_decoder *d, const uint32_t *rec_idx, uint32_t n, uint32_t *out_rows);
+
 /* ---- -b: tagged BAM output (csrc/k_bamtag.h, csrc/bam_decoder_tag.h; DESIGN.md section 7 has the edit rule) ---------------------------------------------------
  * What BamProcessorAbstract::save_alignment (BamProcessorAbstract.cpp:65-114) writes for every accepted alignment: the record with its gene, raw
  * barcode, raw UMI, the two quality strings and the read type as Z tags.  Every aux entry the tag walk reaches whose name is one of the edited
