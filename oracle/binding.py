@@ -75,6 +75,7 @@ def oracle_lib():
         "orc_merge_umis_explicit": (C.c_int, [vp, u64, C.c_char_p, P(C.c_char_p), P(C.c_char_p), C.c_int]),
         "orc_fill_wrong_umi": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int]),
         "orc_directional_targets": (C.c_int, [vp, P(C.c_char_p), vp, C.c_int, C.c_char_p, C.c_char_p, C.c_int]),
+        "orc_directional_sort_order": (C.c_int, [vp, C.c_int, vp]),
         "orc_collisions_table": (C.c_int, [vp, u64, u64, vp]),
         "orc_merge_cells_explicit": (C.c_int, [vp, u64, u64]), "orc_exclude_cell_explicit": (C.c_int, [vp, u64]),
         "orc_count_matrix_levels": (u64, [vp, C.c_char_p, C.c_int, vp, vp, vp]),
@@ -400,6 +401,14 @@ def fill_wrong_umi(umi):
     out = C.create_string_buffer(len(umi) + 1)
     oracle_lib().orc_fill_wrong_umi(umi.encode(), out, len(umi) + 1)
     return out.value.decode()
+
+
+def directional_sort_order(reads):
+    """Positions of `reads` (UMI-index order) after the std::sort of MergeUMIsStrategyDirectional::find_targets"""
+    reads = np.ascontiguousarray(reads, np.uint64)
+    out = np.zeros(len(reads), np.uint32)
+    oracle_lib().orc_directional_sort_order(reads.ctypes.data, len(reads), out.ctypes.data)
+    return [int(x) for x in out]
 
 
 def poisson_upper_tail(k, lam):

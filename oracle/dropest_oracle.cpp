@@ -794,8 +794,11 @@ struct Container {
 		if (has_n && target.empty()) return fix_n_with_random(s.seq);
 		return target;
 	}
-	std::unordered_map<std::string, std::string> directional_targets(std::vector<UmiWrap> &v) const {
+	static void sort_by_reads(std::vector<UmiWrap> &v) {   // :57-58; the arrangement of equal read counts is std::sort's own
 		std::sort(v.begin(), v.end(), [](const UmiWrap &a, const UmiWrap &b) { return a.n_reads < b.n_reads; });
+	}
+	std::unordered_map<std::string, std::string> directional_targets(std::vector<UmiWrap> &v) const {
+		sort_by_reads(v);
 		std::unordered_map<std::string, std::string> out;
 		for (size_t i = 0; i < v.size(); ++i) {
 			std::string t = directional_target(i, v);
@@ -1243,6 +1246,14 @@ int orc_directional_targets(void *h, const char *const *seqs, const uint64_t *re
 		++k;
 	}
 	return k;
+}
+// The sort of find_targets alone: order_out[i] = position in `reads` of the element that ends at sorted position i
+int orc_directional_sort_order(const uint64_t *reads, int n, uint32_t *order_out) {
+	std::vector<orc::Container::UmiWrap> v;
+	for (int i = 0; i < n; ++i) v.push_back({std::to_string(i), size_t(reads[i])});
+	orc::Container::sort_by_reads(v);
+	for (int i = 0; i < n; ++i) order_out[i] = uint32_t(std::stoul(v[size_t(i)].seq));
+	return 0;
 }
 // Tools::CollisionsAdjuster table: adjusted_size[s] for s = 1..max_expr
 int orc_collisions_table(const double *probs, uint64_t n, uint64_t max_expr, uint64_t *out) {
