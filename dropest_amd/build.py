@@ -82,6 +82,7 @@ FILTERED_TOOL = os.path.join(HERE, "..", "tests", "cpp", "bam_filtered")
 FILTERED_SHARDED_TOOL = os.path.join(HERE, "..", "tests", "cpp", "bam_filtered_sharded")
 CORRECTIONS_TOOL = os.path.join(HERE, "..", "tests", "cpp", "read_corrections_dump")
 SOURCES_TOOL = os.path.join(HERE, "..", "tests", "cpp", "bam_sources")
+SOURCES_OUTPUT_TOOL = os.path.join(HERE, "..", "tests", "cpp", "bam_sources_output")
 
 
 def build_facade(force=False, verbose=False):
@@ -107,14 +108,15 @@ def build_facade(force=False, verbose=False):
     filtered_sharded_src = os.path.join(HERE, "..", "tests", "cpp", "bam_filtered_sharded.cpp")
     corrections_src = os.path.join(HERE, "..", "tests", "cpp", "read_corrections_dump.cpp")
     sources_src = os.path.join(HERE, "..", "tests", "cpp", "bam_sources.cpp")
+    sources_output_src = os.path.join(HERE, "..", "tests", "cpp", "bam_sources_output.cpp")
     newest = max(os.path.getmtime(x) for x in (src, rds, bam, bam_ctl, bam_dev, ga, os.path.join(CSRC, "host", "rds_writer.h"), os.path.join(CSRC, "host", "bam_ingest.h"),
                                                os.path.join(CSRC, "host", "bam_parse.h"), os.path.join(CSRC, "host", "bgzf_blocks.h"),
                                                os.path.join(CSRC, "host", "gene_annotation.h"),
-                                               hdr, test_src, bam_tool_src, rate_src, rds_tool_src, sharded_bam_src, validation_src, validation_sharded_src, tagged_src, umi_targets_src, filtered_src, filtered_sharded_src, corrections_src, sources_src, LIB))
+                                               hdr, test_src, bam_tool_src, rate_src, rds_tool_src, sharded_bam_src, validation_src, validation_sharded_src, tagged_src, umi_targets_src, filtered_src, filtered_sharded_src, corrections_src, sources_src, sources_output_src, LIB))
     if not force and os.path.exists(FACADE_LIB) and os.path.exists(FACADE_TEST) and os.path.exists(BAM_TOOL) and os.path.exists(RATE_TOOL) and os.path.exists(RDS_TOOL) and \
-            os.path.exists(SHARDED_BAM_TOOL) and os.path.exists(VALIDATION_TOOL) and os.path.exists(VALIDATION_SHARDED_TOOL) and os.path.exists(TAGGED_TOOL) and os.path.exists(UMI_TARGETS_TOOL) and os.path.exists(FILTERED_TOOL) and os.path.exists(FILTERED_SHARDED_TOOL) and os.path.exists(CORRECTIONS_TOOL) and os.path.exists(SOURCES_TOOL) and \
+            os.path.exists(SHARDED_BAM_TOOL) and os.path.exists(VALIDATION_TOOL) and os.path.exists(VALIDATION_SHARDED_TOOL) and os.path.exists(TAGGED_TOOL) and os.path.exists(UMI_TARGETS_TOOL) and os.path.exists(FILTERED_TOOL) and os.path.exists(FILTERED_SHARDED_TOOL) and os.path.exists(CORRECTIONS_TOOL) and os.path.exists(SOURCES_TOOL) and os.path.exists(SOURCES_OUTPUT_TOOL) and \
             min(os.path.getmtime(FACADE_LIB), os.path.getmtime(FACADE_TEST), os.path.getmtime(BAM_TOOL), os.path.getmtime(RATE_TOOL), os.path.getmtime(RDS_TOOL),
-                os.path.getmtime(SHARDED_BAM_TOOL), os.path.getmtime(VALIDATION_TOOL), os.path.getmtime(VALIDATION_SHARDED_TOOL), os.path.getmtime(TAGGED_TOOL), os.path.getmtime(UMI_TARGETS_TOOL), os.path.getmtime(FILTERED_TOOL), os.path.getmtime(FILTERED_SHARDED_TOOL), os.path.getmtime(CORRECTIONS_TOOL), os.path.getmtime(SOURCES_TOOL)) > newest:
+                os.path.getmtime(SHARDED_BAM_TOOL), os.path.getmtime(VALIDATION_TOOL), os.path.getmtime(VALIDATION_SHARDED_TOOL), os.path.getmtime(TAGGED_TOOL), os.path.getmtime(UMI_TARGETS_TOOL), os.path.getmtime(FILTERED_TOOL), os.path.getmtime(FILTERED_SHARDED_TOOL), os.path.getmtime(CORRECTIONS_TOOL), os.path.getmtime(SOURCES_TOOL), os.path.getmtime(SOURCES_OUTPUT_TOOL)) > newest:
         return FACADE_LIB, FACADE_TEST
     cmds = [
         ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", src, rds, bam, bam_ctl, bam_dev, ga, "-o", FACADE_LIB, "-L" + LIB_DIR, "-ldropest_amd", "-lz",
@@ -144,6 +146,8 @@ def build_facade(force=False, verbose=False):
         ["g++", "-O2", "-std=c++17", "-Wall", corrections_src, "-o", CORRECTIONS_TOOL, "-L" + LIB_DIR, "-ldropest_facade", "-ldropest_amd",
          "-Wl,-rpath,$ORIGIN/../../dropest_amd/lib"],
         ["g++", "-O2", "-std=c++17", "-Wall", sources_src, "-o", SOURCES_TOOL, "-L" + LIB_DIR, "-ldropest_facade", "-ldropest_amd",
+         "-Wl,-rpath,$ORIGIN/../../dropest_amd/lib"],
+        ["g++", "-O2", "-std=c++17", "-Wall", sources_output_src, "-o", SOURCES_OUTPUT_TOOL, "-L" + LIB_DIR, "-ldropest_facade", "-ldropest_amd",
          "-Wl,-rpath,$ORIGIN/../../dropest_amd/lib"],
     ]
     for cmd in cmds:

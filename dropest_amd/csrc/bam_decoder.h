@@ -184,6 +184,7 @@ struct BamTagging {
 
 // The two sources beside a record's own tags and name (k_bamparse.h: BamSources): the caller's read-parameter table (-r; not owned) with the
 // stream ordinal of the next window's first record, and the reference -> gene table of -P.  A reset drops both, as it drops the annotation.
+// ref_off / ref_pool: the references' names for the tag kernels under -P (dropest_bam_decoder_set_reference_names); a reset drops them too.
 struct BamSourceState {
 	dropest_read_params *table = nullptr;
 	uint64_t first_ordinal = 0, seen = 0;      // seen: records of the windows finished since the table was given
@@ -191,7 +192,11 @@ struct BamSourceState {
 	DevBuf<uint32_t> rp_row;
 	DevBuf<int32_t> gene_of_ref;
 	PinnedBuf<uint32_t> h_rp_row;
-	void reset() { table = nullptr; first_ordinal = seen = 0; ref_gene = false; }
+	DevBuf<uint32_t> ref_off;
+	DevBuf<uint8_t> ref_pool;
+	uint32_t n_ref_names = 0;
+	bool has_ref_names = false;
+	void reset() { table = nullptr; first_ordinal = seen = 0; ref_gene = false; has_ref_names = false; n_ref_names = 0; }
 	int bits() const { return (table ? BAM_SRC_PARAMS : 0) | (ref_gene ? BAM_SRC_REF_GENE : 0); }
 };
 

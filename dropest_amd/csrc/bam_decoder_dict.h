@@ -102,7 +102,8 @@ extern "C" int dropest_bam_decoder_set_dictionaries(dropest_bam_decoder *d, cons
 // -r: the records' barcodes, UMIs and UMI quality strings come from `table` (dropest_read_params_*, bam_read_params.h; built, on this GPU; it stays
 // the caller's and outlives the decoder's use of it) by the read's name, each row serving the first record of the stream that asks for it.
 // first_ordinal: the stream ordinal of the next window's first record -- above every ordinal that claimed a row of this table before (the records
-// of the files read so far).  NULL turns the source off; so does a reset.  Not with -f (the tags win there), not with tagged output.
+// of the files read so far; 0 for the first file of a replay, dropest_read_params_replay_begin).  NULL turns the source off; so does a reset.  Not
+// with -f (the tags win there).  A tagging decoder writes CR / UR / the UMI quality from the served row (bam_decoder_tag.h).
 extern "C" int dropest_bam_decoder_set_read_params(dropest_bam_decoder *d, dropest_read_params *table, uint64_t first_ordinal) {
 	return bgzf_guarded([&] {
 		if (!d) throw InvalidError("null argument");
@@ -110,7 +111,6 @@ extern "C" int dropest_bam_decoder_set_read_params(dropest_bam_decoder *d, drope
 		if (!table->built) throw InvalidError("the read-parameter table was not built (dropest_read_params_build)");
 		if (table->device != d->device) throw InvalidError("the read-parameter table lives on another GPU");
 		if (d->cfg.filled_bam) throw InvalidError("read-parameter files are not looked at under -f (barcode and UMI come from the tags)");
-		if (d->tag.on) throw UnsupportedError("tagged output is not written under read-parameter files");
 		d->src.table = table; d->src.first_ordinal = first_ordinal; d->src.seen = 0;
 	});
 }
@@ -123,7 +123,6 @@ extern "C" int dropest_bam_decoder_set_gene_of_reference(dropest_bam_decoder *d,
 		if (!d) throw InvalidError("null argument");
 		if (!gene_of_ref) { d->src.ref_gene = false; return; }
 		if (n_refs != uint32_t(d->cfg.n_refs)) throw InvalidError("one gene per reference is expected");
-		if (d->tag.on) throw UnsupportedError("tagged output is not written under gene = chromosome name");
 		for (uint32_t r = 0; r < n_refs; ++r) if (gene_of_ref[r] < -2) throw InvalidError("a gene index below -2");
 		HIP_CHECK(hipSetDevice(d->device));
 		bam_ready(d);
@@ -131,5 +130,29 @@ extern "C" int dropest_bam_decoder_set_gene_of_reference(dropest_bam_decoder *d,
 		d->src.gene_of_ref.ensure(std::max<uint32_t>(n_refs, 1u));
 		if (n_refs) { size_t at = 0; d->dict.h_dict.ensure(size_t(n_refs) * 4 + 64); bam_to_device(d, d->src.gene_of_ref.p, gene_of_ref, size_t(n_refs) * 4, at); HIP_CHECK(hipStreamSynchronize(d->stream)); }
 		d->src.ref_gene = true;
+	});
+}
+
+// -P with tagged output: the references' names, name r = pool[off[r] .. off[r + 1]) (n + 1 offsets; host memory, copied), which the tag kernels
+// write as the gene of a record on reference r.  A record whose reference id is not below n is flagged, not written (dropest_bam_decoder_tag_window
+// then fails).  n = 0 drops the names; so does a reset.
+extern "C" int dropest_bam_decoder_set_reference_names(dropest_bam_decoder *d, const uint32_t *off, const uint8_t *pool, uint32_t n_names) {
+	return bgzf_guarded([&] {
+		if (!d || (n_names && (!off || (off[n_names] && !pool)))) throw InvalidError("null argument");
+		for (uint32_t r = 0; r < n_names; ++r) if (off[r] > off[r + 1]) throw InvalidError("the reference names' offsets must not decrease");
+		HIP_CHECK(hipSetDevice(d->device));
+		bam_ready(d);
+		HIP_CHECK(hipStreamSynchronize(d->stream));
+		BamSourceState &S = d->src;
+		S.has_ref_names = false; S.n_ref_names = 0;
+		if (!n_names) return;
+		const uint32_t bytes = off[n_names];
+		S.ref_off.ensure(size_t(n_names) + 1); S.ref_pool.ensure(size_t(bytes) + 16);
+		size_t at = 0;
+		d->dict.h_dict.ensure((size_t(n_names) + 1) * 4 + size_t(bytes) + 128);
+		bam_to_device(d, S.ref_off.p, off, (size_t(n_names) + 1) * 4, at);
+		if (bytes) bam_to_device(d, S.ref_pool.p, pool, bytes, at);
+		HIP_CHECK(hipStreamSynchronize(d->stream));
+		S.n_ref_names = n_names; S.has_ref_names = true;
 	});
 }

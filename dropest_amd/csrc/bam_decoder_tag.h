@@ -9,7 +9,6 @@ extern "C" int dropest_bam_decoder_set_tagging(dropest_bam_decoder *d, const dro
 		BamTagging &T = d->tag;
 		T.on = false; T.has_names = false; T.len = 0; T.filt.on = false;      // (-F is configured behind -b: its names are checked against these)
 		if (!cfg) return;
-		if (d->src.bits()) throw UnsupportedError("tagged output is not written under read-parameter files or gene = chromosome name");
 		static_assert(sizeof(BamTagCfg) == 12 + 12 + 72, "the C struct's first members and the kernels' struct are one layout");
 		for (int k = 0; k < 3; ++k) if (cfg->type_len[k] > 24) throw InvalidError("read-type values longer than 24 characters");
 		if (!cfg->out_tag[1] || !cfg->out_tag[2]) throw InvalidError("the raw barcode and raw UMI tags need two-letter names");
@@ -67,15 +66,22 @@ extern "C" int dropest_bam_decoder_patch_annotation(dropest_bam_decoder *d, cons
 	});
 }
 
+// -P: the gene the kernels write is the reference's name, which only the caller has
+static void tag_check_sources(const dropest_bam_decoder *d) {
+	if (d->src.ref_gene && !d->src.has_ref_names) throw InvalidError("under gene = chromosome name the tag kernels need the references' names (dropest_bam_decoder_set_reference_names)");
+}
+
 // the last window's records as the tag kernels read them
 static BamTagIn tag_in(dropest_bam_decoder *d) {
-	const bool ann = d->dict.annotation != nullptr;
+	const bool ann = d->dict.annotation != nullptr && !d->src.ref_gene;      // (-P comes before -g: the parse asked no annotation)
 	return BamTagIn{d->last().data(), d->rec.off.p, d->rec.status.p, d->rec.aux.p, uint32_t(d->at.last_n_rec), ann ? d->ann.gene.p : nullptr, ann ? d->ann.mark.p : nullptr};
 }
 
 // each record's output size, the tiles' sums and every record's place; the wait for the one total that sizes the output (in h_tag)
 // (filt: -F -- every record's rank among the accepted ones first, the sizes by the decisions; segs: the decisions stand in segments)
-static void tag_plan(dropest_bam_decoder *d, hipStream_t st, const BamTagIn &in, const BamTagNames &names, uint32_t grid, uint32_t tiles, const BamTagFilt *filt, const BamTagSegments *segs) {
+// (ts: -r / -P -- the kernels with the sources)
+static void tag_plan(dropest_bam_decoder *d, hipStream_t st, const BamTagIn &in, const BamTagNames &names, uint32_t grid, uint32_t tiles, const BamTagFilt *filt, const BamTagSegments *segs,
+                     const BamTagSrc *ts) {
 	BamTagging &T = d->tag;
 	const uint32_t n_rec = in.n_rec;
 	HIP_CHECK(hipMemsetAsync(T.flags.p, 0, 4, st));
@@ -84,9 +90,13 @@ static void tag_plan(dropest_bam_decoder *d, hipStream_t st, const BamTagIn &in,
 		hipLaunchKernelGGL(bam_tag_rank_tile_kernel, dim3(tiles), dim3(256), 0, st, in.status, n_rec, T.filt.tile_ok.p);
 		hipLaunchKernelGGL(bam_tag_rank_scan_kernel, dim3(1), dim3(1024), 0, st, T.filt.tile_ok.p, tiles, T.filt.total.p);
 		hipLaunchKernelGGL(bam_tag_rank_kernel, dim3(tiles), dim3(256), 0, st, in.status, n_rec, T.filt.tile_ok.p, T.filt.rank.p);
-		if (segs) hipLaunchKernelGGL(bam_tag_filter_plan_kernel<BamTagSegments>, dim3(grid), dim3(BAMTAG_T), 0, st, in, d->cfg, T.cfg, names, *filt, T.size.p, T.flags.p, *segs);
+		if (ts && segs) hipLaunchKernelGGL((bam_tag_sources_plan_kernel<true, BamTagSegments>), dim3(grid), dim3(BAMTAG_T), 0, st, in, d->cfg, T.cfg, names, *filt, T.size.p, T.flags.p, *segs, *ts);
+		else if (ts) hipLaunchKernelGGL((bam_tag_sources_plan_kernel<true, BamTagOneArray>), dim3(grid), dim3(BAMTAG_T), 0, st, in, d->cfg, T.cfg, names, *filt, T.size.p, T.flags.p, BamTagOneArray{}, *ts);
+		else if (segs) hipLaunchKernelGGL(bam_tag_filter_plan_kernel<BamTagSegments>, dim3(grid), dim3(BAMTAG_T), 0, st, in, d->cfg, T.cfg, names, *filt, T.size.p, T.flags.p, *segs);
 		else hipLaunchKernelGGL(bam_tag_filter_plan_kernel<BamTagOneArray>, dim3(grid), dim3(BAMTAG_T), 0, st, in, d->cfg, T.cfg, names, *filt, T.size.p, T.flags.p, BamTagOneArray{});
-	} else
+	} else if (ts)
+		hipLaunchKernelGGL((bam_tag_sources_plan_kernel<false, BamTagOneArray>), dim3(grid), dim3(BAMTAG_T), 0, st, in, d->cfg, T.cfg, names, BamTagFilt{}, T.size.p, T.flags.p, BamTagOneArray{}, *ts);
+	else
 		hipLaunchKernelGGL(bam_tag_plan_kernel, dim3(grid), dim3(BAMTAG_T), 0, st, in, d->cfg, T.cfg, names, T.size.p, T.flags.p);
 	hipLaunchKernelGGL(bam_tag_tile_sum_kernel, dim3(tiles), dim3(256), 0, st, T.size.p, n_rec, T.tile_bytes.p, T.tile_written.p);
 	hipLaunchKernelGGL(bam_tag_tile_scan_kernel, dim3(1), dim3(1024), 0, st, T.tile_bytes.p, T.tile_written.p, tiles, T.flags.p, T.h_tag.p);
@@ -112,10 +122,17 @@ static void tag_run(dropest_bam_decoder *d, const BamTagFilt *filt, const uint8_
 	T.h_tag.ensure(4);
 	for (hipEvent_t &e : T.ev) if (!e) HIP_CHECK(hipEventCreate(&e));
 	const BamTagIn in = tag_in(d);
-	const BamTagNames names{d->dict.annotation ? T.name_off.p : nullptr, T.name_pool.p, T.n_names};
+	const BamTagNames names{in.a_gene ? T.name_off.p : nullptr, T.name_pool.p, T.n_names};
 	const uint32_t grid = uint32_t((n_rec + BAMTAG_WAVES - 1) / BAMTAG_WAVES);
-	tag_plan(d, st, in, names, grid, tiles, filt, segs);
+	// -r / -P: the served rows and the table's text, the references' names (the table is not in use by anything else: its calls' own rule)
+	const BamSourceState &S = d->src;
+	const dropest_read_params *const tb = S.table;
+	const BamTagSrc sources{S.bits(), S.rp_row.p, tb ? tb->rows.p : nullptr, tb ? tb->text.p : nullptr, tb ? tb->n_rows : 0u, tb ? tb->text_len : 0ull,
+	                        BamTagNames{S.ref_off.p, S.ref_pool.p, S.n_ref_names}};
+	const BamTagSrc *const ts = sources.bits ? &sources : nullptr;
+	tag_plan(d, st, in, names, grid, tiles, filt, segs, ts);
 	const uint64_t total = T.h_tag.p[0], written = T.h_tag.p[1];
+	if (ts && (T.h_tag.p[2] & BAMTAG_FLAG_RANGE)) throw RangeError("a record that is written names a read-parameter row, an extent of the table's text or a reference that does not exist (or its decision a cell or a side string)");
 	if (T.h_tag.p[2] & BAMTAG_FLAG_RANGE) throw RangeError("the decision of a read that is written names a cell or a side string that does not exist");      // (or no segment covers it: never, the counts were checked)
 	if (T.h_tag.p[2] & BAMTAG_FLAG_UNDECIDED) {
 		undecided = true;
@@ -126,7 +143,11 @@ static void tag_run(dropest_bam_decoder *d, const BamTagFilt *filt, const uint8_
 	if (filt && !total) return;                  // (-F: no read of this window is written)
 	T.out.ensure(size_t(total) + size_t(total) / 8 + 64);
 	HIP_CHECK(hipEventRecord(T.ev[2], st));      // (the kernels' time: the host's wait and the allocation between them are not theirs)
-	if (filt && segs) hipLaunchKernelGGL(bam_tag_filter_emit_kernel<BamTagSegments>, dim3(grid), dim3(BAMTAG_T), 0, st, in, d->cfg, T.cfg, names, *filt, T.size.p, T.off.p, T.out.p, total, T.flags.p, *segs);
+	const BamTagFilt no_filt{};
+	if (ts && segs) hipLaunchKernelGGL((bam_tag_sources_emit_kernel<true, BamTagSegments>), dim3(grid), dim3(BAMTAG_T), 0, st, in, d->cfg, T.cfg, names, *filt, T.size.p, T.off.p, T.out.p, total, T.flags.p, *segs, *ts);
+	else if (ts && filt) hipLaunchKernelGGL((bam_tag_sources_emit_kernel<true, BamTagOneArray>), dim3(grid), dim3(BAMTAG_T), 0, st, in, d->cfg, T.cfg, names, *filt, T.size.p, T.off.p, T.out.p, total, T.flags.p, BamTagOneArray{}, *ts);
+	else if (ts) hipLaunchKernelGGL((bam_tag_sources_emit_kernel<false, BamTagOneArray>), dim3(grid), dim3(BAMTAG_T), 0, st, in, d->cfg, T.cfg, names, no_filt, T.size.p, T.off.p, T.out.p, total, T.flags.p, BamTagOneArray{}, *ts);
+	else if (filt && segs) hipLaunchKernelGGL(bam_tag_filter_emit_kernel<BamTagSegments>, dim3(grid), dim3(BAMTAG_T), 0, st, in, d->cfg, T.cfg, names, *filt, T.size.p, T.off.p, T.out.p, total, T.flags.p, *segs);
 	else if (filt) hipLaunchKernelGGL(bam_tag_filter_emit_kernel<BamTagOneArray>, dim3(grid), dim3(BAMTAG_T), 0, st, in, d->cfg, T.cfg, names, *filt, T.size.p, T.off.p, T.out.p, total, T.flags.p, BamTagOneArray{});
 	else hipLaunchKernelGGL(bam_tag_emit_kernel, dim3(grid), dim3(BAMTAG_T), 0, st, in, d->cfg, T.cfg, names, T.size.p, T.off.p, T.out.p, total, T.flags.p);
 	HIP_CHECK(hipGetLastError());
@@ -146,6 +167,7 @@ extern "C" int dropest_bam_decoder_tag_window(dropest_bam_decoder *d, const uint
 		BamTagging &T = d->tag;
 		if (!T.on) throw InvalidError("tagging is not configured for this decoder (dropest_bam_decoder_set_tagging)");
 		if (d->dict.annotation && !T.has_names) throw InvalidError("with an annotation the tagging configuration must bring its gene names");
+		tag_check_sources(d);
 		T.len = 0;
 		if (!d->at.last_n_rec) return;
 		HIP_CHECK(hipSetDevice(d->device));
@@ -206,6 +228,7 @@ extern "C" int dropest_bam_decoder_filter_window(dropest_bam_decoder *d, const u
 		if (!T.on) throw InvalidError("tagging is not configured for this decoder (dropest_bam_decoder_set_tagging)");
 		if (!F.on) throw InvalidError("filtering is not configured for this decoder (dropest_bam_decoder_set_filtering)");
 		if (d->dict.annotation && !T.has_names) throw InvalidError("with an annotation the tagging configuration must bring its gene names");
+		tag_check_sources(d);
 		T.len = 0;
 		if (n != d->at.last_n_ok) throw InvalidError(std::to_string(n) + " decisions for a window of " + std::to_string(d->at.last_n_ok) + " accepted records");
 		const uint64_t n_rec = d->at.last_n_rec;
@@ -253,6 +276,7 @@ extern "C" int dropest_bam_decoder_filter_window_segments(dropest_bam_decoder *d
 		if (!T.on) throw InvalidError("tagging is not configured for this decoder (dropest_bam_decoder_set_tagging)");
 		if (!F.on) throw InvalidError("filtering is not configured for this decoder (dropest_bam_decoder_set_filtering)");
 		if (d->dict.annotation && !T.has_names) throw InvalidError("with an annotation the tagging configuration must bring its gene names");
+		tag_check_sources(d);
 		T.len = 0;
 		uint64_t n = 0;
 		bool wraps = false;

@@ -15,11 +15,15 @@ struct dropest_read_params {
 	std::vector<Lines> calls;
 	DevBuf<uint8_t> text;
 	DevBuf<unsigned long long> line_be, claim;
+	DevBuf<unsigned long long> replay_claim;      // _replay_begin .. _replay_end: the claims of a second pass over the stream, `claim` untouched beside them
+	bool replaying = false;
+	unsigned long long text_len = 0;
+	unsigned long long *claims() const { return replaying ? replay_claim.p : claim.p; }
 	DevBuf<RpRow> rows;
 	DevBuf<uint32_t> slots, canonical, counts;
 	uint32_t n_rows = 0, mask = 63, h_counts[3] = {0, 0, 0};
 	bool built = false;
-	RpTable view() const { return RpTable{slots.p, mask, rows.p, text.p, claim.p, hash_mask}; }
+	RpTable view() const { return RpTable{slots.p, mask, rows.p, text.p, claims(), hash_mask}; }
 };
 
 static dropest_read_params *rp_built(dropest_read_params *t) {
@@ -66,7 +70,7 @@ extern "C" int dropest_read_params_build(dropest_read_params *t) {
 		while (uint64_t(cap) < 2ull * n) cap <<= 1;
 		t->text.alloc(t->h_text.size() + 16); t->line_be.alloc(size_t(n) * 2 + 2); t->rows.alloc(size_t(n) + 1); t->claim.alloc(size_t(n) + 1);
 		t->canonical.alloc(size_t(n) + 1); t->slots.alloc(cap); t->counts.alloc(4);
-		t->n_rows = n; t->mask = cap - 1;
+		t->n_rows = n; t->mask = cap - 1; t->text_len = t->h_text.size();
 		if (!t->h_text.empty()) HIP_CHECK(hipMemcpy(t->text.p, t->h_text.data(), t->h_text.size(), hipMemcpyHostToDevice));
 		if (n) HIP_CHECK(hipMemcpy(t->line_be.p, t->h_line_be.data(), size_t(n) * 16, hipMemcpyHostToDevice));
 		HIP_CHECK(hipMemset(t->slots.p, 0, size_t(cap) * 4));
@@ -134,7 +138,7 @@ extern "C" int dropest_read_params_claims_to_host(dropest_read_params *t, uint64
 		if (!n) return;
 		if (!out) throw InvalidError("null argument");
 		HIP_CHECK(hipDeviceSynchronize());
-		HIP_CHECK(hipMemcpy(out, t->claim.p + first, size_t(n) * 8, hipMemcpyDeviceToHost));
+		HIP_CHECK(hipMemcpy(out, t->claims() + first, size_t(n) * 8, hipMemcpyDeviceToHost));
 	});
 }
 
@@ -142,8 +146,32 @@ extern "C" int dropest_read_params_reset_claims(dropest_read_params *t) {
 	return bgzf_guarded([&] {
 		rp_built(t);
 		HIP_CHECK(hipDeviceSynchronize());
-		HIP_CHECK(hipMemset(t->claim.p, 0xFF, (size_t(t->n_rows) + 1) * 8));
+		HIP_CHECK(hipMemset(t->claims(), 0xFF, (size_t(t->n_rows) + 1) * 8));
 		HIP_CHECK(hipDeviceSynchronize());
+	});
+}
+
+// A second pass over the same stream (-F: the reference makes a new parser for write_filtered_bam_files, so every row serves afresh): from _begin to
+// _end the table's claims are a fresh array, all ones, and the array that was current stays as it is beside it; _end puts it back.  Whatever reads
+// or writes claims in between (a decoder's windows, _claims_to_host, _reset_claims) works on the fresh array.
+extern "C" int dropest_read_params_replay_begin(dropest_read_params *t) {
+	return bgzf_guarded([&] {
+		rp_built(t);
+		if (t->replaying) throw InvalidError("the read-parameter table is in a replay already (dropest_read_params_replay_end)");
+		HIP_CHECK(hipDeviceSynchronize());
+		t->replay_claim.ensure(size_t(t->n_rows) + 1);
+		HIP_CHECK(hipMemset(t->replay_claim.p, 0xFF, (size_t(t->n_rows) + 1) * 8));
+		HIP_CHECK(hipDeviceSynchronize());
+		t->replaying = true;
+	});
+}
+
+extern "C" int dropest_read_params_replay_end(dropest_read_params *t) {
+	return bgzf_guarded([&] {
+		rp_built(t);
+		if (!t->replaying) throw InvalidError("the read-parameter table is not in a replay (dropest_read_params_replay_begin)");
+		HIP_CHECK(hipDeviceSynchronize());
+		t->replaying = false;
 	});
 }
 

@@ -252,10 +252,11 @@ void BamController::parse_bam_files(const std::vector<std::string> &bam_files, b
 	const BamSwitches sw = BamSwitches::from_environment();
 	_tagged.clear();
 	_saved_per_file.clear();
+	const bool source_output = _device_read_sources && _device_source_output;      // -b / -F under -r and -P: the tag kernels read the row and the reference's name
 	if (print_result_bams) {      // what the device path refuses, said before any file is read: the host reader does not write BAM
 		const char *why = nullptr;
-		if (_params_from_files) why = "read-parameter files (-r) are served by the host reader";
-		else if (_gene_in_chromosome_name) why = "gene = chromosome name is resolved by the host reader";
+		if (_params_from_files && !source_output) why = "read-parameter files (-r) are served by the host reader";
+		else if (_gene_in_chromosome_name && !source_output) why = "gene = chromosome name is resolved by the host reader";
 		else if (_tags.intronic_read_value.size() > 24 || _tags.intergenic_read_value.size() > 24 || _tags.exonic_read_value.size() > 24) why = "a read-type value is longer than 24 bytes";
 		if (why) throw std::runtime_error(std::string("Tagged BAM output (-b) is written on the device BAM path only, which this configuration cannot take: ") + why);
 		_tagged.reserve(bam_files.size());
@@ -265,7 +266,8 @@ void BamController::parse_bam_files(const std::vector<std::string> &bam_files, b
 	join_release_thread();
 	for (auto const &bam_name : bam_files) {
 		FileIngest file(sw, bam_name, bam_files.size(), container, _counters, _tags, _filled_bam, _params_from_files, _gene_in_chromosome_name, _min_barcode_phred, _genes, nthreads);
-		file.device_sources = _device_read_sources && !print_result_bams;
+		file.device_sources = _device_read_sources && (!print_result_bams || source_output);
+		file.source_output = source_output;
 		if (file.device_sources && _params_from_files && !_param_source->host_served && !_param_source->text.empty()) file.params = _param_source.get();
 		struct NoteSaved { std::vector<size_t> &per_file; const Counters &c; size_t before; ~NoteSaved() { per_file.push_back(c.saved - before); } } note{_saved_per_file, _counters, _counters.saved};
 		if (print_result_bams) { _tagged.emplace_back(); file.tagged = &_tagged.back(); }
@@ -287,9 +289,10 @@ void BamController::parse_bam_files(const std::vector<std::string> &bam_files, b
 void BamController::write_filtered_bam_files(const std::vector<std::string> &bam_files, CellsDataContainer &container) {
 	const BamSwitches sw = BamSwitches::from_environment();
 	_filtered = FilteredFile();
+	const bool source_output = _device_read_sources && _device_source_output;
 	const char *why = nullptr;
-	if (_params_from_files) why = "read-parameter files (-r) are served by the host reader";
-	else if (_gene_in_chromosome_name) why = "gene = chromosome name is resolved by the host reader";
+	if (_params_from_files && !source_output) why = "read-parameter files (-r) are served by the host reader";
+	else if (_gene_in_chromosome_name && !source_output) why = "gene = chromosome name is resolved by the host reader";
 	else if (_tags.intronic_read_value.size() > 24 || _tags.intergenic_read_value.size() > 24 || _tags.exonic_read_value.size() > 24) why = "a read-type value is longer than 24 bytes";
 	if (why) throw std::runtime_error(std::string("Filtered BAM output (-F) is written on the device BAM path only, which this configuration cannot take: ") + why);
 	if (bam_files.empty()) return;
@@ -306,6 +309,8 @@ void BamController::write_filtered_bam_files(const std::vector<std::string> &bam
 			const size_t k = size_t(&bam_name - &bam_files.front());
 			FileIngest file(sw, bam_name, bam_files.size(), container, second_pass, _tags, _filled_bam, _params_from_files, _gene_in_chromosome_name, _min_barcode_phred, _genes, 1);
 			file.filtered = pass;
+			file.device_sources = file.source_output = source_output;
+			if (source_output && _params_from_files && !_param_source->host_served && !_param_source->text.empty()) file.params = _param_source.get();
 			if (!read_file_on_device(file))
 				throw std::runtime_error("Filtered BAM output (-F) is written on the device BAM path only, which cannot take this file: " + (file.refusal.empty() ? std::string("unknown reason") : file.refusal) + ": " + bam_name);
 			const uint64_t brought = filtered_pass_reads(pass) - before;

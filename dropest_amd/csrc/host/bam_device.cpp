@@ -12,6 +12,9 @@
 // is on.  With it, -r is a table on the device (ParamSource::table_on; csrc/k_readparams.h) that every record's name is looked up in and that
 // serves each row once, to the first record of the stream that asks -- the decoder says which row each record was served, and the strings of the
 // few records the host must see are spelled from the row's line; -P is a table reference -> gene index (gene_of_reference_to_device).
+// Behind BamController::set_device_source_output the two outputs below are written under -r and -P too: the tag kernels read the served row's
+// strings from the table and the reference's name from a table of names (tagging_to_decoder), and the -F pass serves the rows afresh on claims of
+// its own (filtered_pass_replay .. filtered_pass_close).
 // Tagged BAM output (-b: parse_bam_files(files, true, container)) is made here and only here: every window's accepted records are edited on the device
 // (csrc/k_bamtag.h) before the window goes into the container, compressed there and written to `<input stem>.tagged.bam` (open_tagged, tag_window,
 // close_tagged); a file this path refuses is then an error that names the reason (FileIngest::refusal), not a file for the host reader.
@@ -122,6 +125,8 @@ struct FilteredPass {
 	std::vector<Piece> pieces;
 	size_t cur = 0;                  // the shard the current file's decoder sits with: the one that holds the file's first read
 	std::string name;
+	ParamSource *replay = nullptr;   // -r: the table's claims are the pass's own (filtered_pass_replay) until end_replay puts the ingest's back
+	uint64_t ingest_ordinal = 0;     // ... and the ordinal the ingest had come to
 	std::FILE *f = nullptr;
 	dropest_deflate_stream *z = nullptr;
 	int z_device = -1; void *z_stream = nullptr;      // where the compressor runs: the decoder's GPU and stream
@@ -130,7 +135,14 @@ struct FilteredPass {
 	size_t windows = 0;
 	double decode_ms = 0, tag_ms = 0, decisions_ms = 0;
 	FilteredPass(const BamSwitches &sw, CellsDataContainer &container, BamController::FilteredFile &report) : sw(sw), container(container), report(report) {}
-	~FilteredPass() { if (z) dropest_deflate_stream_destroy(z); if (f) std::fclose(f); }
+	~FilteredPass() { (void)end_replay(); if (z) dropest_deflate_stream_destroy(z); if (f) std::fclose(f); }
+	bool end_replay() {
+		if (!replay) return true;
+		ParamSource *const src = replay;
+		replay = nullptr;
+		src->ordinal = ingest_ordinal;
+		return dropest_read_params_replay_end(src->table) == 0;
+	}
 	static int write(const uint8_t *bytes, uint64_t len, void *user) { return std::fwrite(bytes, 1, size_t(len), static_cast<FilteredPass *>(user)->f) == size_t(len) ? 0 : 1; }
 	[[noreturn]] void other_files(const std::string &what) const {
 		throw std::runtime_error("Filtered BAM output (-F): " + what + ": these are not the files the container was filled from (the same files, in the same order)");
@@ -197,6 +209,13 @@ FilteredPass *filtered_pass_open(const BamSwitches &sw, CellsDataContainer &cont
 	return p.release();
 }
 
+void filtered_pass_replay(FilteredPass *pass, ParamSource &params) {
+	if (pass->replay) return;
+	if (dropest_read_params_replay_begin(params.table)) throw std::runtime_error(std::string("Filtered BAM output (-F): read parameters: ") + dropest_bgzf_last_error());
+	pass->replay = &params; pass->ingest_ordinal = params.ordinal;
+	params.ordinal = 0;
+}
+
 uint64_t filtered_pass_reads(const FilteredPass *pass) { return pass->at; }
 uint64_t filtered_pass_total(const FilteredPass *pass) { return pass->n_reads; }
 void filtered_pass_other_files(const FilteredPass *pass, const std::string &what) { pass->other_files(what); }
@@ -209,8 +228,10 @@ void filtered_pass_close(FilteredPass *pass, bool ok) {
 		if (p->z) { dropest_deflate_stream_destroy(p->z); p->z = nullptr; }
 		if (p->f) { std::fclose(p->f); p->f = nullptr; std::remove(p->name.c_str()); }
 	};
+	const bool claims_back = p->end_replay();      // (first thing, and whichever way the pass ended: the ingest's claims are the table's again)
 	if (!ok) { drop(); return; }
 	try {
+		if (!claims_back) throw std::runtime_error(std::string("Filtered BAM output (-F): read parameters: ") + dropest_bgzf_last_error());
 		if (p->at != p->n_reads) p->other_files("the files hold " + std::to_string(p->at) + " accepted reads, the container " + std::to_string(p->n_reads));
 		if (p->written != p->counts[0]) throw std::runtime_error("internal: " + std::to_string(p->written) + " reads were written to the filtered BAM file, the container's decisions write " + std::to_string(p->counts[0]));
 		if (!p->z) throw std::runtime_error("internal: no filtered BAM file was opened");
@@ -518,6 +539,12 @@ void DeviceFileReader::tagging_to_decoder() {
 		tc.gene_name_off = off.data(); tc.gene_name_pool = pool.data(); tc.n_gene_names = uint32_t(flat.gene_names.size());
 	}
 	if (dropest_bam_decoder_set_tagging(dec, &tc)) fail();
+	if (parser.gene_in_chromosome_name) {      // -P: the gene the kernels write is the reference's name
+		std::vector<uint32_t> r_off(1, 0); std::vector<uint8_t> r_pool;
+		for (const std::string &r : file.refs) { r_pool.insert(r_pool.end(), r.begin(), r.end()); r_off.push_back(uint32_t(r_pool.size())); }
+		r_pool.push_back(0);
+		if (r_pool.size() > 0xFFFFFFF0ull || dropest_bam_decoder_set_reference_names(dec, r_off.data(), r_pool.data(), uint32_t(file.refs.size()))) fail();
+	}
 }
 
 // (c) -b: `<input stem>.tagged.bam` in the current directory (BamProcessor::get_result_bam_name, BamProcessorAbstract::update_bam strips the
@@ -1013,7 +1040,7 @@ bool DeviceFileReader::read() {
 
 bool read_file_on_device(FileIngest &file) {
 	const RecordParser &parser = file.parser;
-	const bool output = file.tagged || file.filtered;      // (-b and -F under -r or -P: the tag kernels would need the row's strings and the chromosome's name)
+	const bool output = (file.tagged || file.filtered) && !file.source_output;      // (-b and -F under -r or -P: only behind BamController::set_device_source_output)
 	if (parser.params_from_files && (!file.params || output)) { file.refusal = "read-parameter files (-r) are served by the host reader"; return false; }
 	if (parser.gene_in_chromosome_name && (!file.device_sources || output)) { file.refusal = "gene = chromosome name is resolved by the host reader"; return false; }
 	// (-b stays here whatever the container takes: a window it cannot take in bulk goes through records_through_host, record by record if need be)
@@ -1029,6 +1056,7 @@ bool read_file_on_device(FileIngest &file) {
 	// -r: the table on the GPU this file's decoder will sit on (a container over several GPUs may want another one than the table's: the claims
 	// would have to be carried over -- the host reader takes the file instead)
 	if (file.params && !file.params->table_on(target.device)) { file.refusal = "the read-parameter table cannot be held on this file's GPU"; return false; }
+	if (file.params && file.filtered) filtered_pass_replay(file.filtered, *file.params);      // (before the pass's first file claims anything)
 	DeviceFileReader reader(file, target, t_enter);
 	return reader.read();
 }

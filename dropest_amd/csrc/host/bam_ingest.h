@@ -107,7 +107,7 @@ private:
 	bool _params_from_files = false;
 	std::shared_ptr<struct ParamSource> _param_source;            // -r: the files' inflated text and, on the device path, its table (bam_parse.h)
 	bool _read_params_mapped = false;
-	bool _device_read_sources = false;
+	bool _device_read_sources = false, _device_source_output = false;
 	void load_read_params(const std::string &filenames);
 	void map_read_params();
 	void serve_read_params(Parsed &pr);
@@ -133,8 +133,9 @@ public:
 	// `<input stem>.tagged.bam` in the current directory (BamProcessor::get_result_bam_name, BamProcessorAbstract::update_bam), with its gene, raw
 	// barcode ("CR"), raw UMI ("UR"), quality strings and read type as Z tags (BamProcessorAbstract::save_alignment; DESIGN.md section 7 has the
 	// rule).  The records are edited on the device (csrc/k_bamtag.h) and compressed there (include/dropest_deflate.h), so the device reader is used
-	// whether or not DROPEST_BAM_DEVICE is set, and what it refuses -- -r parameter files, gene = chromosome name, a read-type value over 24
-	// bytes, no GPU -- throws std::runtime_error naming the reason: the host reader does not write BAM.  false: the call above.
+	// whether or not DROPEST_BAM_DEVICE is set, and what it refuses -- -r parameter files and gene = chromosome name (unless
+	// set_device_source_output is on), a read-type value over 24 bytes, no GPU -- throws std::runtime_error naming the reason: the host reader
+	// does not write BAM.  false: the call above.
 	void parse_bam_files(const std::vector<std::string> &bam_files, bool print_result_bams, CellsDataContainer &container);
 	const std::vector<TaggedFile> &tagged_files() const { return _tagged; }   // of the last parse_bam_files call
 	// BamController::write_filtered_bam_files (BamController.cpp:38-48; -F), after container.merge_and_filter(): the same files are read again, and
@@ -146,8 +147,8 @@ public:
 	// edited and compressed on the device and nothing is added to the container; read i of the container is the i-th record the files'
 	// readers accept, so the files must be the ones the container was filled from, in that order: a window that would pass the container's
 	// read count, or a final count that differs from it, throws std::runtime_error saying so; and when this controller filled the container
-	// (its last parse_bam_files call accepted exactly the container's reads) every file must bring the reads it brought then.  Device path only, like -b: -r parameter files,
-	// gene = chromosome name, a read-type value over 24 bytes, no GPU throw naming the reason; a sharded or split container (unless
+	// (its last parse_bam_files call accepted exactly the container's reads) every file must bring the reads it brought then.  Device path only, like -b: -r parameter files
+	// and gene = chromosome name (unless set_device_source_output is on), a read-type value over 24 bytes, no GPU throw naming the reason; a sharded or split container (unless
 	// set_sharded_filtered_output is on) and UMI-dictionary mode throw with the read corrections' own message.
 	void write_filtered_bam_files(const std::vector<std::string> &bam_files, CellsDataContainer &container);
 	// -F over a sharded or split container (off by default: write_filtered_bam_files then refuses such a container as before).  On: the shards
@@ -166,10 +167,18 @@ public:
 	// go to the host reader, as before).  -r: the files' rows become a table on the container's GPU (include/dropest_bgzf.h:
 	// dropest_read_params_*), probed by every record's name there, each row serving the first record of the stream that asks, as the host
 	// reader's map does; -P: the reference's name is the gene, a constant per record.  The answer is the host reader's.  Tagged and filtered
-	// output (-b, -F) under -r or -P stay refused either way.  A file the device path cannot take after all (no GPU, a container over several
+	// output (-b, -F) under -r or -P stay refused unless set_device_source_output is on as well.  A file the device path cannot take after all (no GPU, a container over several
 	// GPUs whose next read lives on another GPU than the table) goes to the host reader with the rows the device served taken out of its map;
 	// from then on the host reader serves every later file.  DESIGN.md section 7.
 	void set_device_read_sources(bool on) { _device_read_sources = on; }
+	// Tagged and filtered output (-b, -F) under -r and -P, on the device path (off by default: both are refused with the texts they always had; on,
+	// together with set_device_read_sources).  -r: the raw barcode, the raw UMI and the UMI quality tag of a written record are the fields of the
+	// row the record was served, as they stand in the line; NO barcode quality tag is written (ReadParametersEfficient::parameters answers "" for
+	// it) and an entry of that name stays in the record.  -P: the gene tag is the reference's name and the read is exonic; an empty name writes
+	// neither tag.  -F serves the rows afresh from the first file on, as the reference's new parser does, on claims of its own: the ingest's
+	// claims are what they were when the call returns or throws.  Still refused, with the reason: a table that cannot be held on the file's GPU,
+	// parameter files the host reader has served from, and what the read corrections refuse (UMI-dictionary mode).  DESIGN.md section 7.
+	void set_device_source_output(bool on) { _device_source_output = on; }
 	// the device path keeps one decoder per GPU (streams, 2-7 GB of device buffers, up to 512 MB of pinned staging) between the files of one
 	// parse_bam_files call; they are given back on a helper thread when the call ends (DROPEST_BAM_KEEP_DECODERS=1: kept for the next call).
 	// This waits for that thread and frees whatever is still cached.

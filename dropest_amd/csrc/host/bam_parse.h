@@ -342,7 +342,8 @@ struct FileIngest {
 	BamController::TaggedFile *tagged = nullptr;   // -b: this file's tagged BAM is to be written (device path only); what was written is noted here
 	struct FilteredPass *filtered = nullptr;       // -F: the file is read for write_filtered_bam_files -- nothing goes into the container
 	std::string refusal;                 // why the device path handed the file back (read_file_on_device returned false)
-	bool device_sources = false;         // BamController::set_device_read_sources: the device path may take the file under -r and -P (ingest only)
+	bool device_sources = false;         // BamController::set_device_read_sources: the device path may take the file under -r and -P
+	bool source_output = false;          // BamController::set_device_source_output: ... and write its tagged / filtered records there
 	ParamSource *params = nullptr;       // -r with that switch: the rows for the device path's table
 	FileIngest(const BamSwitches &sw, const std::string &bam_name, size_t n_files, CellsDataContainer &container, BamController::Counters &counters,
 	           const BamTags &tags, bool filled_bam, bool params_from_files, bool gene_in_chromosome_name, int min_barcode_phred,
@@ -359,6 +360,9 @@ struct FileIngest {
 struct FilteredPass;
 FilteredPass *filtered_pass_open(const BamSwitches &sw, CellsDataContainer &container, BamController::FilteredFile &report, bool sharded_output);
 void filtered_pass_close(FilteredPass *pass, bool ok);
+// -r: the pass serves the rows afresh, as the reference's new parser does -- from the first file on the table's claims are an array of the pass's
+// own and the stream ordinals restart at 0 (dropest_read_params_replay_begin); _close puts both back, however the pass ended.  Once per pass.
+void filtered_pass_replay(FilteredPass *pass, ParamSource &params);
 uint64_t filtered_pass_reads(const FilteredPass *pass);      // accepted records of the files read so far
 uint64_t filtered_pass_total(const FilteredPass *pass);      // the container's reads
 [[noreturn]] void filtered_pass_other_files(const FilteredPass *pass, const std::string &what);

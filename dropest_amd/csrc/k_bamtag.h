@@ -37,6 +37,13 @@
 // range meets the window; the segment of a rank is found by a ballot over 64 table entries a step, wave-uniform like everything else here.
 // Measured: rank + plan + scan + emit 64.5 ms for 16 M records of which 13.7 M are written (-b in the same job: 59.1 ms for all 16 M);
 // 3-9 % of the -F pass, of which the compressor is 71-81 %.
+//
+// The sources beside the record (-r, -P: BAM_SRC_*, k_bamparse.h) are one more template parameter of bamtag_record and bamtag_inputs (SRCS) and
+// kernels of their own on top of them (bam_tag_sources_plan / _emit): with -r the raw barcode, the raw UMI and the UMI quality are three extents of
+// the read-parameter table's text -- the row the settle served the record (BamSources::rp_row), loaded wave-uniformly like everything else the walk
+// decides by -- and no barcode quality is written (ReadParametersEfficient::parameters answers "" for it); with -P the gene is the name of the
+// record's reference and the mark what the parse left in o_aux.  Which of the two is on is a wave-uniform test of BamTagSrc::bits, not a template
+// parameter: one instantiation per decision source, not four.  The kernels without sources are untouched: SRCS = false compiles to what they were.
 #pragma once
 
 #include "k_bamparse.h"
@@ -82,6 +89,17 @@ struct BamTagValue { const uint8_t *str; unsigned long long code; uint32_t len; 
 struct BamTagFix { uint32_t name[2]; BamTagValue v[2]; };
 
 __device__ inline uint32_t bt_u(uint32_t v) { return uint32_t(__builtin_amdgcn_readfirstlane(int(v))); }
+__device__ inline unsigned long long bt_u64(unsigned long long v) { return (unsigned long long)bt_u(uint32_t(v)) | ((unsigned long long)bt_u(uint32_t(v >> 32)) << 32); }
+
+// -r / -P (SRCS): where a record's strings come from when not from the record.  bits: BAM_SRC_*.  -r: rp_row[r] = the row of `rows` that record r was
+// served (bam_params_settle_kernel), whose extents lie in text[0 .. text_len); -P: reference k's name = refs.pool[refs.off[k] .. refs.off[k + 1])
+struct BamTagSrc {
+	int bits;
+	const uint32_t *rp_row; const RpRow *rows; const uint8_t *text; uint32_t n_rows; unsigned long long text_len;
+	BamTagNames refs;
+};
+// the served row's raw barcode, raw UMI and UMI quality (on: the record's own name and tags are not asked for them)
+struct BamTagRowStrings { const uint8_t *s[3]; uint32_t len[3]; bool on; };
 
 // One aux entry whose name starts at tags + o (o + 3 <= n): name, type and the length of its value (which starts at o + 3).  false: the walk stops
 // here -- an unknown type, a string without its NUL, a value past the record's end (BamRecord::get_string_tags; tests/bam_model.py: string_tags).
@@ -157,9 +175,10 @@ template <bool EMIT> struct BamTagOut {
 
 // Record `rec` (its block_size field first, accepted by bam_parse) -> the bytes of its output (block_size field included), counted or written.
 // FILT (-F): the two values of `fx` follow the read type, under the same rule (a value of no character is not written and drops nothing).
-template <bool EMIT, bool FILT = false>
+// SRCS with rs.on (-r): raw barcode, raw UMI and UMI quality are the row's; no barcode quality; the record's name and those four tags are not looked at.
+template <bool EMIT, bool FILT = false, bool SRCS = false>
 __device__ inline uint32_t bamtag_record(const uint8_t *rec, uint32_t lane, const BamParseCfg &pc, const BamTagCfg &tc, uint32_t mark, const uint8_t *gene_override, uint32_t gene_override_len,
-                                         bool use_override, uint8_t *dst, uint32_t cap, bool &over, const BamTagFix &fx = BamTagFix{}) {
+                                         bool use_override, uint8_t *dst, uint32_t cap, bool &over, const BamTagFix &fx = BamTagFix{}, const BamTagRowStrings &rs = BamTagRowStrings{}) {
 	const uint32_t block_size = bt_u(b_le32(rec));
 	const uint8_t *p = rec + 4;
 	const uint32_t l_read_name = bt_u(p[8]), n_cigar = bt_u(b_le16(p + 12)), l_seq = bt_u(b_le32(p + 16));
@@ -177,6 +196,7 @@ __device__ inline uint32_t bamtag_record(const uint8_t *rec, uint32_t lane, cons
 		if (!bamtag_entry(tags, tags_size, o, lane, name, type, len, text)) break;
 #pragma unroll
 		for (int k = 0; k < 6; ++k) {
+			if (SRCS && rs.on && k < 4) continue;
 			if (pc.tag[k] != name || !pc.tag[k] || found[k] || closed[k]) continue;
 			if (text) { val[k] = tags + o + 3; vlen[k] = len - 1; found[k] = true; }
 			else if (type == 'A') { val[k] = tags + o + 3; vlen[k] = 1; found[k] = true; }
@@ -189,7 +209,9 @@ __device__ inline uint32_t bamtag_record(const uint8_t *rec, uint32_t lane, cons
 	const uint8_t *src[5]; uint32_t sl[5];
 #pragma unroll
 	for (int k = 0; k < 5; ++k) { src[k] = nullptr; sl[k] = 0; }
-	if (pc.filled_bam) {
+	if (SRCS && rs.on) {
+		src[1] = rs.s[0]; sl[1] = rs.len[0]; src[2] = rs.s[1]; sl[2] = rs.len[1]; src[4] = rs.s[2]; sl[4] = rs.len[2];
+	} else if (pc.filled_bam) {
 		src[1] = val[T_CB]; sl[1] = vlen[T_CB]; src[2] = val[T_UMI]; sl[2] = vlen[T_UMI];
 		if (found[T_CBQ]) { src[3] = val[T_CBQ]; sl[3] = vlen[T_CBQ]; }
 		if (found[T_UMIQ]) { src[4] = val[T_UMIQ]; sl[4] = vlen[T_UMIQ]; }
@@ -253,7 +275,11 @@ __device__ inline uint32_t bamtag_record(const uint8_t *rec, uint32_t lane, cons
 }
 
 // the record's gene under -g and its mark; false: not an accepted record
-__device__ inline bool bamtag_inputs(const BamTagIn &in, const BamTagNames &names, uint32_t r, uint32_t &mark, const uint8_t *&g, uint32_t &g_len, bool &use_override, uint32_t *flags, uint32_t lane) {
+// SRCS: -P, the gene is the name of the record's reference (the mark is o_aux's already); -r, the served row's three strings into `rs`.  Everything is
+// checked before it is loaded (as bamtag_decision does): a reference or a row outside its table, an extent past the text -> BAMTAG_FLAG_RANGE, false
+template <bool SRCS = false>
+__device__ inline bool bamtag_inputs(const BamTagIn &in, const BamTagNames &names, uint32_t r, uint32_t &mark, const uint8_t *&g, uint32_t &g_len, bool &use_override, uint32_t *flags, uint32_t lane,
+                                     const BamTagSrc *ts = nullptr, BamTagRowStrings *rs = nullptr) {
 	if (bt_u(in.status[r]) != BAM_OK) return false;
 	mark = bt_u(in.o_aux[r] >> 16);
 	g = nullptr; g_len = 0; use_override = names.off != nullptr;
@@ -261,6 +287,28 @@ __device__ inline bool bamtag_inputs(const BamTagIn &in, const BamTagNames &name
 		if (bt_u(uint32_t(in.a_mark[r])) == uint32_t(-2)) { if (lane == 0) atomicOr(flags, BAMTAG_FLAG_UNDECIDED); }      // more genes at an end point than annotate_reads holds: the host decided, the device cannot name the gene
 		const uint32_t ag = bt_u(in.a_gene[r]);
 		if (ag < names.n) { const uint32_t a = bt_u(names.off[ag]); g = names.pool + a; g_len = bt_u(names.off[ag + 1]) - a; }
+	}
+	if (SRCS) {
+		bool ok = true;
+		rs->on = false;
+		if (ts->bits & BAM_SRC_REF_GENE) {
+			const uint32_t ref = bt_u(b_le32(in.data + in.rec_off[r] + 4));
+			use_override = true; g = nullptr; g_len = 0;
+			if (ref < ts->refs.n) { const uint32_t a = bt_u(ts->refs.off[ref]), b = bt_u(ts->refs.off[ref + 1]); g = ts->refs.pool + a; g_len = b > a ? b - a : 0u; }
+			else ok = false;
+		}
+		if (ts->bits & BAM_SRC_PARAMS) {
+			const uint32_t row = bt_u(ts->rp_row[r]);
+			if (row < ts->n_rows) {
+				const RpRow &w = ts->rows[row];
+				const unsigned long long off[3] = {bt_u64(w.cb_off), bt_u64(w.umi_off), bt_u64(w.quality_off)};
+				rs->len[0] = bt_u(w.cb_len); rs->len[1] = bt_u(w.umi_len); rs->len[2] = bt_u(w.quality_len);
+#pragma unroll
+				for (int k = 0; k < 3; ++k) { ok = ok && off[k] <= ts->text_len && rs->len[k] <= ts->text_len - off[k]; rs->s[k] = ts->text + off[k]; }
+				rs->on = true;
+			} else ok = false;
+		}
+		if (!ok) { if (lane == 0) atomicOr(flags, BAMTAG_FLAG_RANGE); return false; }
 	}
 	return true;
 }
@@ -304,8 +352,6 @@ __global__ __launch_bounds__(BAMTAG_T) void bam_tag_emit_kernel(BamTagIn in, Bam
 }
 
 // ---- -F: a record's decision ------------------------------------------------------------------------------------------------------------
-__device__ inline unsigned long long bt_u64(unsigned long long v) { return (unsigned long long)bt_u(uint32_t(v)) | ((unsigned long long)bt_u(uint32_t(v >> 32)) << 32); }
-
 // a code -> the value to write; false: an escaped code whose side string does not exist (nothing of it is loaded)
 __device__ inline bool bamtag_value(unsigned long long code, const BamTagFilt &f, BamTagValue &v) {
 	v.str = nullptr; v.code = code; v.len = 0;
@@ -402,6 +448,42 @@ __global__ __launch_bounds__(BAMTAG_T) void bam_tag_filter_emit_kernel(BamTagIn 
 	BamTagFix fx;
 	if (!bamtag_decision(in, filt, src, r, fx, flags, lane) || !bamtag_inputs(in, names, r, mark, g, g_len, use_override, flags, lane)) return;
 	bamtag_record<true, true>(in.data + in.rec_off[r], lane, pc, tc, mark, g, g_len, use_override, out + at, cap, over, fx);
+	if (over && lane == 0) atomicOr(flags, BAMTAG_FLAG_SIZE);
+}
+
+// ---- -r / -P: the four kernels above with the sources (SRCS) -----------------------------------------------------------------------------------
+// FILT = false: bam_tag_plan / _emit (filt and src are not looked at: BamTagFilt{}, BamTagOneArray{}); FILT = true: bam_tag_filter_plan / _emit<SRC>.
+template <bool FILT, class SRC>
+__global__ __launch_bounds__(BAMTAG_T) void bam_tag_sources_plan_kernel(BamTagIn in, BamParseCfg pc, BamTagCfg tc, BamTagNames names, BamTagFilt filt, uint32_t *__restrict__ size,
+                                                                         uint32_t *__restrict__ flags, SRC src, BamTagSrc ts) {
+	const uint32_t lane = threadIdx.x & 63u;
+	const uint32_t r = bt_u(blockIdx.x * BAMTAG_WAVES + (threadIdx.x >> 6));
+	if (r >= in.n_rec) return;
+	uint32_t mark, g_len; const uint8_t *g; bool use_override, over = false;
+	uint32_t bytes = 0;
+	BamTagFix fx{};
+	BamTagRowStrings rs;
+	if ((!FILT || bamtag_decision(in, filt, src, r, fx, flags, lane)) && bamtag_inputs<true>(in, names, r, mark, g, g_len, use_override, flags, lane, &ts, &rs))
+		bytes = bamtag_record<false, FILT, true>(in.data + in.rec_off[r], lane, pc, tc, mark, g, g_len, use_override, nullptr, 0u, over, fx, rs);
+	if (lane == 0) size[r] = bytes;
+}
+
+template <bool FILT, class SRC>
+__global__ __launch_bounds__(BAMTAG_T) void bam_tag_sources_emit_kernel(BamTagIn in, BamParseCfg pc, BamTagCfg tc, BamTagNames names, BamTagFilt filt, const uint32_t *__restrict__ size,
+                                                                         const uint64_t *__restrict__ out_off, uint8_t *__restrict__ out, uint64_t out_total, uint32_t *__restrict__ flags, SRC src,
+                                                                         BamTagSrc ts) {
+	const uint32_t lane = threadIdx.x & 63u;
+	const uint32_t r = bt_u(blockIdx.x * BAMTAG_WAVES + (threadIdx.x >> 6));
+	if (r >= in.n_rec) return;
+	const uint32_t cap = bt_u(size[r]);
+	if (!cap) return;
+	const uint64_t at = out_off[r];
+	if (at + cap > out_total) { if (lane == 0) atomicOr(flags, BAMTAG_FLAG_SIZE); return; }
+	uint32_t mark, g_len; const uint8_t *g; bool use_override, over = false;
+	BamTagFix fx{};
+	BamTagRowStrings rs;
+	if ((FILT && !bamtag_decision(in, filt, src, r, fx, flags, lane)) || !bamtag_inputs<true>(in, names, r, mark, g, g_len, use_override, flags, lane, &ts, &rs)) return;
+	bamtag_record<true, FILT, true>(in.data + in.rec_off[r], lane, pc, tc, mark, g, g_len, use_override, out + at, cap, over, fx, rs);
 	if (over && lane == 0) atomicOr(flags, BAMTAG_FLAG_SIZE);
 }
 

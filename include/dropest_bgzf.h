@@ -188,18 +188,32 @@ int dropest_read_params_lookup(dropest_read_params *t, const uint8_t *name_pool,
  * a claim is consumed, for the table's life or until _reset_claims. */
 int dropest_read_params_claims_to_host(dropest_read_params *t, uint64_t first, uint64_t n, uint64_t *out);
 int dropest_read_params_reset_claims(dropest_read_params *t);
+/* A second pass over the same stream (-F: the reference makes a new parser for write_filtered_bam_files, ReadMapParamsParser and all, so every row
+ * serves afresh).  _replay_begin puts a fresh claim array, all ones, in the table's place for claims; the array that was current stays untouched
+ * beside it and _replay_end puts it back.  In between every decoder window, _claims_to_host and _reset_claims work on the fresh array, and the
+ * first file's decoder is given first_ordinal 0 (dropest_bam_decoder_set_read_params: the caller counts, as ever).  One replay at a time. */
+int dropest_read_params_replay_begin(dropest_read_params *t);
+int dropest_read_params_replay_end(dropest_read_params *t);
 void dropest_read_params_destroy(dropest_read_params *t);
 /* The decoder takes barcode, UMI and UMI quality of every record from `table` (same GPU; stays the caller's) by the read's name, one '@' off.  A
  * record that is neither skipped nor on an unknown reference claims the row it finds with its stream ordinal: first_ordinal + the records of the
  * windows finished since this call + its index in the window.  A launch behind the parse serves the record whose ordinal stands in the claim: no
  * row, or a row claimed by an earlier record -> DROPEST_BAM_CANT_PARSE; a row that fails the quality filter -> DROPEST_BAM_LOW_QUALITY (the row is
  * taken all the same); else the row's codes and quality string are the record's (a code of 0 makes it a need record).  first_ordinal must lie above
- * every ordinal that claimed a row of the table before.  NULL turns it off, as a reset does.  Refused under -f and with tagged output. */
+ * every ordinal that claimed a row of the table before.  NULL turns it off, as a reset does.  Refused under -f.  With tagged output
+ * (dropest_bam_decoder_set_tagging, in either order) the raw barcode, the raw UMI and the UMI quality tag of a written record are the served row's
+ * fields as they stand in the line; no barcode quality tag is written (ReadParametersEfficient::parameters answers "" for it) and an entry of
+ * that name stays in the record. */
 int dropest_bam_decoder_set_read_params(dropest_bam_decoder *d, dropest_read_params *table, uint64_t first_ordinal);
 /* -P (gene = chromosome name, ReadParamsParser.cpp:42-48): gene_of_ref[r] = index of reference r's name in the caller's gene dictionary, -1 = not in
  * it yet (a record on r is a need record; send the table again once the dictionary has grown), -2 = the name is empty (no gene, mark 0).  Other
  * records carry mark HAS_EXONS.  Comes before an annotation and the gene tag; the read type is not looked at.  NULL turns it off, as a reset does. */
 int dropest_bam_decoder_set_gene_of_reference(dropest_bam_decoder *d, const int32_t *gene_of_ref, uint32_t n_refs);
+/* -P with tagged output: the references' names, name r = pool[off[r] .. off[r + 1]) (n_names + 1 offsets; HOST memory, copied), which the tag
+ * kernels write as the gene tag of a record on reference r (an empty name: no gene tag, no read type).  .._tag_window / .._filter_window* under -P
+ * without them fail and name this call.  A written record whose reference id is not below n_names makes them fail too (nothing is loaded from
+ * there).  n_names = 0 drops the names, as a reset does. */
+int dropest_bam_decoder_set_reference_names(dropest_bam_decoder *d, const uint32_t *off, const uint8_t *pool, uint32_t n_names);
 /* For records rec_idx[0 .. n) of the LAST window (NULL: its first n records): the row of the table each was served (a row that fails the quality
  * filter included), 0xFFFFFFFF for every other record. */
 int dropest_bam_decoder_param_rows(dropest_bam_decoder *d, const uint32_t *rec_idx, uint32_t n, uint32_t *out_rows);
